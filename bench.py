@@ -9,8 +9,21 @@ resident in HBM.  Weights are the formula weights of stts2_mi355x.synth (the Lib
 checkpoint is download-only); inputs are synthetic with the SURVEY.md §8(d) distributions.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 32] [--frames 400]
-                    [--decoder hifigan|istftnet] [--dtype bf16|fp32] [--no-cpu-baseline]
-                    [--no-profile] [--no-parity-mode] [--no-e2e]
+                    [--decoder hifigan|istftnet] [--dtype bf16|fp32] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-profile] [--no-parity-mode] [--no-accuracy-mode] [--no-e2e]]
+
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the result line
+(`value` = samples/s over the K timed steps, `ms_per_step` = their wall time / K).  --full adds every other
+figure, each in runs of its own after the timed steps: the per-launch profiled pass and the dominant kernel's
+roofline, the fp32 parity mode and the bf16x3 accuracy mode on the same workload, the PCIe-inclusive
+host-to-host figure, the CPU baseline (oracle, B = 1 and B = 4) and, with N > 1, the RCCL gather and
+scatter + gather figures.  The --no-* options leave single legs out of a --full run.
+
+--dump-outputs DIR writes what the last timed step computed, as a caller of the decoder receives it, to
+DIR/audio.npy (float32 [N x B, 1, 600 T], every rank's utterances gathered to rank 0).  Weights, inputs and the
+per-step noise seed are formulas of the arguments, so two builds run with the same arguments decode the same
+inputs and their files compare element for element.  An output above 64 MB is written as a fixed sample of
+it (the flat indices drawn by numpy's default_rng(0), ascending, the same for every run of one shape).
 
 N GPUs = N processes, one per GPU (config 4, BASELINE configs[3]): when WORLD_SIZE is not set
 and N > 1, this process spawns `torch.distributed.run --nproc-per-node N` as a child (it never
@@ -179,6 +192,25 @@ def spawn(args_list, n):
     return subprocess.call(cmd)
 
 
+DUMP_LIMIT = 64 * 2 ** 20  # bytes --dump-outputs may write in all
+
+
+def dump_outputs(dirpath, arrays):
+    """{name: tensor} -> dirpath/<name>.npy, float32 (float64 kept), DUMP_LIMIT bytes in all; a larger tensor is
+    written as its values at a fixed seeded sample of flat indices (ascending)."""
+    os.makedirs(dirpath, exist_ok=True)
+    budget = DUMP_LIMIT // max(len(arrays), 1)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.dtype not in (torch.float32, torch.float64):
+            t = t.float()
+        keep = budget // t.element_size()
+        if t.numel() > keep:
+            idx = np.sort(np.random.default_rng(0).choice(t.numel(), size=keep, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(dirpath, name + ".npy"), t.cpu().numpy())
+
+
 class Stand_in:
     """--selftest-cpu: the decoder's output contract ([B,1,600T] float32, a pure function of the
     GLOBAL utterance ids and the step seed) without a GPU."""
@@ -200,8 +232,13 @@ def main():
     ap.add_argument("--frames", type=int, default=400, help="asr frames per utterance (400 = 10 s)")
     ap.add_argument("--decoder", default="hifigan", choices=["hifigan", "istftnet"])
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32", "bf16x3"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's audio to DIR/audio.npy (float32, at most 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the profiled pass + roofline, the fp32 and bf16x3 modes, "
+                         "the PCIe-inclusive figure, the CPU baseline and (N > 1) the gather figures")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="(--full) skip the per-launch profiled pass")
     ap.add_argument("--no-parity-mode", action="store_true", help="skip the fp32 figure of the same workload")
     ap.add_argument("--no-accuracy-mode", action="store_true", help="skip the bf16x3 figure of the same workload")
     ap.add_argument("--no-e2e", action="store_true", help="skip the host-to-host (PCIe-inclusive) figure")
@@ -291,11 +328,16 @@ def main():
     samples = global_batch * 600 * T * args.steps
     value = samples / el
     ms = el / args.steps * 1e3
+    if args.dump_outputs is not None:  # the last timed step's audio, before any later leg decodes into `out` again
+        last = shard.gather_to_rank0(out, world, rank) if dist else out
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"audio": last})
+        del last
 
     # second figure: the same steps with every rank's audio gathered to rank 0 over RCCL
     with_gather = None
     with_scatter_gather = None
-    if dist:
+    if dist and args.full:
         elg, _ = timed(step, args.steps, 1, gather=True)
         with_gather = {"value": samples / elg, "ms_per_step": elg / args.steps * 1e3,
                        "gathered_bytes_per_step": global_batch * 600 * T * 4}
@@ -327,7 +369,7 @@ def main():
             np.save(args.dump_checksum, full.cpu().numpy())
 
     prof_recs = None
-    if not cpu and not args.no_profile:  # per-launch hipEvents: a separate pass, not the timed one
+    if not cpu and args.full and not args.no_profile:  # per-launch hipEvents: a separate pass, not the timed one
         # the timed pass runs the production options (the noise branches on a side stream beside the front-end and
         # the stages, STTS_OPT_NBRANCH); this pass runs every conv launch alone, so that its hipEvent duration
         # prices the kernel rather than the overlap
@@ -341,7 +383,7 @@ def main():
         E.profile_enable(False)
         E.set_option(E.OPT_NBRANCH, nb0)
     parity = None
-    if not cpu and not args.no_parity_mode and args.dtype != "fp32":
+    if not cpu and args.full and not args.no_parity_mode and args.dtype != "fp32":
         # the north-star accuracy mode (fp32 storage + exact-fp32 MFMA, 10-s max-abs 2.7e-6 vs the
         # reference) on the same workload
         peng = dec.engine("fp32")
@@ -352,7 +394,7 @@ def main():
                   "mfma_fraction": ALG[args.decoder]["flops"] * global_batch * 600 * T * 3 / elp / PEAK_MFMA["fp32"]}
         dec.engine(args.dtype)
     accuracy = None
-    if not cpu and not args.no_accuracy_mode and args.dtype == "bf16":
+    if not cpu and args.full and not args.no_accuracy_mode and args.dtype == "bf16":
         # the split-operand accuracy mode (fp32 storage, conv operands as bf16 hi + lo on the bf16 MFMA:
         # 10-s max-abs 2.5e-5 vs the reference, tests/test_gpu_split.py) on the same workload
         aeng = dec.engine("bf16x3")
@@ -375,7 +417,7 @@ def main():
             accuracy["roofline"] = roofline(arecs, "bf16x3", 2, accuracy["ms_per_step"], B, T, args.decoder)
         dec.engine(args.dtype)
     e2e = None
-    if not cpu and not args.no_e2e:
+    if not cpu and args.full and not args.no_e2e:
         # host -> host: pinned host inputs copied in, decoded, audio copied back (PCIe included)
         pins = [torch.from_numpy(a).pin_memory() for a in host_in]
         hout = torch.empty(B, 1, 600 * T).pin_memory()
@@ -429,7 +471,7 @@ def main():
         line["accuracy_mode"] = accuracy
     if e2e:
         line["e2e_pcie"] = e2e
-    if not cpu and not args.no_cpu_baseline and world == 1:
+    if not cpu and args.full and not args.no_cpu_baseline and world == 1:
         line["cpu_baseline"] = cpu_baseline(args.decoder, dec.cpu(), cfg, T)
     print(json.dumps(line), flush=True)
     if dist:
