@@ -239,6 +239,55 @@ int stts_smooth_l1_loss(const float* x, const float* y, long long n, double* los
 int stts_smooth_l1_loss_bwd(const float* x, const float* y, long long n, const float* g, float* dx, float* dy,
                             void* stream);
 
+/* ---- The Vocos decoder under the G step (Modules/vocos.py; csrc/vocos_train.hip).  Frames [B][L][C] fp32. */
+
+/* ConvNeXtBlock.dwconv (vocos.py:45): depthwise Conv1d(C, C, K, padding K / 2, groups C) + bias,
+ * y[b][t][c] = bias[c] + sum_k w[c][k] x[b][t + k - K / 2][c] (zero padded); w [C][K] (the reference's [C][1][K]),
+ * bias [C] or NULL.  K odd, 1 <= K <= 11; 1 <= C <= 65536 (any count: no multiple of the 256-channel block is
+ * needed); B <= 65535.  Outside these: STTS_EINVAL (the workspace query returns it as a negative size).
+ * _bwd: dx = the same conv of dy with the taps reversed; dw [C][K] and db [C] as fp64 row-slice partial sums
+ * folded in slice order (each of dx, dw, db may be NULL; x is read for dw, w for dx).
+ * Workspace (dw / db only) >= stts_dwconv1d_bwd_workspace_bytes(B, L, C, K) = B S C (K + 1) doubles rounded up to
+ * 256 bytes, S = min(64, ceil(L / 32)) row slices per utterance. */
+int stts_dwconv1d_fwd(const float* x, const float* w, const float* bias, int B, int L, int C, int K, float* y,
+                      void* stream);
+long long stts_dwconv1d_bwd_workspace_bytes(int B, int L, int C, int K);
+int stts_dwconv1d_bwd(const float* x, const float* w, const float* dy, int B, int L, int C, int K, float* dx, float* dw,
+                      float* db, void* ws, long long ws_bytes, void* stream);
+
+/* nn.GELU() (erf form, vocos.py:48) over n values: y = x Phi(x); _bwd from the saved pre-activation x:
+ * dx = dy (Phi(x) + x phi(x)).  16-byte accesses when the pointers are 16-byte aligned; any n. */
+int stts_gelu_fwd(const float* x, long long n, float* y, void* stream);
+int stts_gelu_bwd(const float* x, const float* dy, long long n, float* dx, void* stream);
+
+/* Layer scale + residual (vocos.py:64-68): y = r + gamma[c] x.  _bwd: dx = gamma dy and dgamma [C] = the column
+ * sums of dy x (fp64 row-slice partials in slice order), each nullable; the residual's gradient is dy itself.
+ * Workspace (dgamma only) >= stts_layer_scale_res_bwd_workspace_bytes(B, L, C) = S C doubles rounded up to 256
+ * bytes, S = min(256, max(1, B L / 16)) row slices. */
+int stts_layer_scale_res_fwd(const float* x, const float* r, const float* gamma, int B, int L, int C, float* y,
+                             void* stream);
+long long stts_layer_scale_res_bwd_workspace_bytes(int B, int L, int C);
+int stts_layer_scale_res_bwd(const float* x, const float* gamma, const float* dy, int B, int L, int C, float* dx,
+                             float* dgamma, void* ws, long long ws_bytes, void* stream);
+
+/* ISTFTHead.forward after its Linear + ISTFT.forward, padding "same" (vocos.py:282-296, :190-232):
+ * h [B][F][2 nb] (nb = n_fft / 2 + 1 log-magnitude channels, then nb phase channels), window [n_fft] ->
+ * audio [B][F hop]:  mag = min(exp(h_k), 100), X_k = mag (cos p_k + i sin p_k), frame = irfft(X) window (the
+ * imaginary parts of DC and Nyquist dropped), audio[j] = sum_t frame[t][j + pad - t hop] / env[j + pad] with env the
+ * overlap-added squared window and pad = (n_fft - hop) / 2.  One workgroup per frame, a two-factor DFT in LDS:
+ * n_fft even, n_fft = N1 N2 with both factors <= 64 (1200 = 30 x 40, 1024 = 32 x 32), 0 < hop < n_fft,
+ * n_fft - hop even; otherwise STTS_EINVAL.
+ * _bwd: dh [B][F][2 nb] from dy [B][F hop], the exact adjoint (dframe gathered from dy, one sample per element, a
+ * forward DFT, then the chain through cos / sin / exp; the clip passes the gradient where exp(h_k) <= 100, as
+ * torch.clip).  The window is a buffer: no gradient.
+ * Workspace >= stts_istft_head_workspace_bytes(B, F, n_fft, hop) = B F n_fft floats rounded up to 256 bytes (the
+ * frames of the forward; _bwd takes the same arguments and uses none of it, so NULL is accepted there). */
+long long stts_istft_head_workspace_bytes(int B, int F, int n_fft, int hop);
+int stts_istft_head_fwd(const float* h, const float* window, int B, int F, int n_fft, int hop, float* audio, void* ws,
+                        long long ws_bytes, void* stream);
+int stts_istft_head_bwd(const float* h, const float* window, const float* dy, int B, int F, int n_fft, int hop,
+                        float* dh, void* ws, long long ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -86,6 +86,17 @@ def _tl():
         "stts_spatial_mean_bwd": ([vp, i, i, i, vp, vp], i),
         "stts_smooth_l1_loss": ([vp, vp, ll, vp, vp], i),
         "stts_smooth_l1_loss_bwd": ([vp, vp, ll, vp, vp, vp, vp], i),
+        "stts_dwconv1d_fwd": ([vp, vp, vp, i, i, i, i, vp, vp], i),
+        "stts_dwconv1d_bwd_workspace_bytes": ([i, i, i, i], ll),
+        "stts_dwconv1d_bwd": ([vp, vp, vp, i, i, i, i, vp, vp, vp, vp, ll, vp], i),
+        "stts_gelu_fwd": ([vp, ll, vp, vp], i),
+        "stts_gelu_bwd": ([vp, vp, ll, vp, vp], i),
+        "stts_layer_scale_res_fwd": ([vp, vp, vp, i, i, i, vp, vp], i),
+        "stts_layer_scale_res_bwd_workspace_bytes": ([i, i, i], ll),
+        "stts_layer_scale_res_bwd": ([vp, vp, vp, i, i, i, vp, vp, vp, ll, vp], i),
+        "stts_istft_head_workspace_bytes": ([i, i, i, i], ll),
+        "stts_istft_head_fwd": ([vp, vp, i, i, i, i, vp, vp, ll, vp], i),
+        "stts_istft_head_bwd": ([vp, vp, vp, i, i, i, i, vp, vp, ll, vp], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -587,14 +598,14 @@ def adain_resblk1d_frames(m, x, s, dtype="fp32"):
     p_drop = float(p_drop or 0.0) if m.training else 0.0
     r = adain_act(x, s, m.norm1.fc.weight, m.norm1.fc.bias, None, ACT_LRELU)
     if up:
-        r = _PoolFn.apply(r, weight_norm(m.pool.weight_g, m.pool.weight_v), m.pool.bias)
+        r = _PoolFn.apply(r, _wn_w(m.pool), m.pool.bias)
     c1, c2 = m.conv1, m.conv2
-    r = conv1d_frames(dropout(r, p_drop), weight_norm(c1.weight_g, c1.weight_v), c1.bias, 1, 1, dtype=dtype)
+    r = conv1d_frames(dropout(r, p_drop), _wn_w(c1), c1.bias, 1, 1, dtype=dtype)
     r = dropout(adain_act(r, s, m.norm2.fc.weight, m.norm2.fc.bias, None, ACT_LRELU), p_drop)
     sc = _Up2Fn.apply(x) if up else x
     if m.learned_sc:
-        sc = conv1d_frames(sc, weight_norm(m.conv1x1.weight_g, m.conv1x1.weight_v), None, 1, 0, dtype=dtype)
-    return conv1d_frames(r, weight_norm(c2.weight_g, c2.weight_v), c2.bias, 1, 1, dtype=dtype, residual=sc,
+        sc = conv1d_frames(sc, _wn_w(m.conv1x1), None, 1, 0, dtype=dtype)
+    return conv1d_frames(r, _wn_w(c2), c2.bias, 1, 1, dtype=dtype, residual=sc,
                          scale=1 / math.sqrt(2))
 
 
@@ -1028,6 +1039,11 @@ def stft_mag(wave, n_fft, hop, win):
 
 # ---------------------------------------------------------------------- decoder (Modules/hifigan.py)
 def _wn_w(layer):
+    """The folded weight of a weight-normed layer in either layout: torch.nn.utils.weight_norm's weight_g / weight_v
+    (hifigan.py) or parametrizations.weight_norm's parametrizations.weight.original0 (g) / original1 (v) (vocos.py:10)."""
+    if hasattr(layer, "parametrizations"):
+        p = layer.parametrizations["weight"]
+        return weight_norm(p.original0, p.original1)
     return weight_norm(layer.weight_g, layer.weight_v)
 
 
@@ -1115,7 +1131,17 @@ def decoder_forward(dec, asr, F0_curve, N, s, noise=None, seed=None, utt_offset=
         seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if noise is None else 0
     if dec.training:
         F0_curve, N = train_smooth(F0_curve, N)
-    B, _, T = asr.shape
+    B = asr.shape[0]
+    x = _decoder_frontend(dec, asr, F0_curve, N, s, dtype)
+    y = generator_forward(dec.generator, x, s, F0_curve, noise, seed, utt_offset, dtype)  # [B, L, 1]
+    return y.reshape(B, 1, -1)
+
+
+def _decoder_frontend(dec, asr, F0_curve, N, s, dtype):
+    """The front-end the three decoders share (hifigan.py:458-472 == vocos.py:404-418): the stride-2 F0 / N convs,
+    encode, asr_res and the decode blocks with their concats -> frames [B, 2T, 512].  Reads either weight-norm
+    layout (_wn_w)."""
+    T = asr.shape[2]
     if F0_curve.shape[-1] != 2 * T or N.shape[-1] != 2 * T:
         raise ValueError(f"F0_curve / N {tuple(F0_curve.shape)} / {tuple(N.shape)}: expected [B, {2 * T}]")
     F0 = conv1d_frames(F0_curve.unsqueeze(-1), _wn_w(dec.F0_conv), dec.F0_conv.bias, 2, 1, 1, dtype)  # [B, T, 1]
@@ -1132,8 +1158,190 @@ def decoder_forward(dec, asr, F0_curve, N, s, noise=None, seed=None, utt_offset=
         x = adain_resblk1d_frames(block, x, s, dtype)
         if block.upsample_type != "none":
             res = False
-    y = generator_forward(dec.generator, x, s, F0_curve, noise, seed, utt_offset, dtype)  # [B, L, 1]
-    return y.reshape(B, 1, -1)
+    return x
+
+
+# ---------------------------------------------------------------------- Vocos decoder (Modules/vocos.py)
+class _DWConvFn(torch.autograd.Function):
+    """ConvNeXtBlock.dwconv (vocos.py:45): depthwise Conv1d(C, C, K, padding K // 2) on frames [B, L, C]; w [C, 1, K]."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias):
+        _require_device()
+        B, L, C = x.shape
+        K = w.shape[-1]
+        xc, wc, bc = _f32(x), _f32(w).reshape(C, K), (_f32(bias) if bias is not None else None)
+        y = torch.empty_like(xc)
+        check(_tl().stts_dwconv1d_fwd(_ptr(xc), _ptr(wc), _ptr(bc), B, L, C, K, _ptr(y), _stream()),
+              "stts_dwconv1d_fwd")
+        ctx.save_for_backward(xc, wc)
+        ctx.w_shape, ctx.has_b = w.shape, bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        xc, wc = ctx.saved_tensors
+        B, L, C = xc.shape
+        K = wc.shape[1]
+        dy = _f32(gy)
+        nx, nw, nbias = ctx.needs_input_grad
+        dx = torch.empty_like(xc) if nx else None
+        dw = torch.empty(C, K, dtype=torch.float32, device=dy.device) if nw else None
+        db = torch.empty(C, dtype=torch.float32, device=dy.device) if (nbias and ctx.has_b) else None
+        nb = _tl().stts_dwconv1d_bwd_workspace_bytes(B, L, C, K)
+        check(int(nb) if nb < 0 else 0, "stts_dwconv1d_bwd_workspace_bytes")
+        ws = _ws(nb, dy.device)
+        check(_tl().stts_dwconv1d_bwd(_ptr(xc), _ptr(wc), _ptr(dy), B, L, C, K, _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws),
+                                      int(nb), _stream()), "stts_dwconv1d_bwd")
+        return dx, (dw.reshape(ctx.w_shape) if dw is not None else None), db
+
+
+def dwconv1d_frames(x, weight, bias=None):
+    return _DWConvFn.apply(x, weight, bias)
+
+
+class _GeluFn(torch.autograd.Function):
+    """nn.GELU() (erf form, vocos.py:48); the backward reads the saved pre-activation."""
+
+    @staticmethod
+    def forward(ctx, x):
+        _require_device()
+        xc = _f32(x)
+        y = torch.empty_like(xc)
+        check(_tl().stts_gelu_fwd(_ptr(xc), xc.numel(), _ptr(y), _stream()), "stts_gelu_fwd")
+        ctx.save_for_backward(xc)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        (xc,) = ctx.saved_tensors
+        dy = _f32(gy)
+        dx = torch.empty_like(xc)
+        check(_tl().stts_gelu_bwd(_ptr(xc), _ptr(dy), xc.numel(), _ptr(dx), _stream()), "stts_gelu_bwd")
+        return dx
+
+
+def gelu(x):
+    return _GeluFn.apply(x)
+
+
+class _LayerScaleResFn(torch.autograd.Function):
+    """y = r + gamma x on frames [B, L, C] (vocos.py:64-68); the residual's gradient is dy itself."""
+
+    @staticmethod
+    def forward(ctx, x, r, gamma):
+        _require_device()
+        B, L, C = x.shape
+        xc, rc, gc = _f32(x), _f32(r), _f32(gamma)
+        if rc.shape != xc.shape or gc.numel() != C:
+            raise ValueError(f"layer scale: x {tuple(x.shape)}, r {tuple(r.shape)}, gamma {tuple(gamma.shape)}")
+        y = torch.empty_like(xc)
+        check(_tl().stts_layer_scale_res_fwd(_ptr(xc), _ptr(rc), _ptr(gc), B, L, C, _ptr(y), _stream()),
+              "stts_layer_scale_res_fwd")
+        ctx.save_for_backward(xc, gc)
+        ctx.g_shape = gamma.shape
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        xc, gc = ctx.saved_tensors
+        B, L, C = xc.shape
+        dy = _f32(gy)
+        nx, nr, ng = ctx.needs_input_grad
+        dx = torch.empty_like(xc) if nx else None
+        dg = torch.empty(C, dtype=torch.float32, device=dy.device) if ng else None
+        nb = _tl().stts_layer_scale_res_bwd_workspace_bytes(B, L, C)
+        check(int(nb) if nb < 0 else 0, "stts_layer_scale_res_bwd_workspace_bytes")
+        ws = _ws(nb, dy.device)
+        check(_tl().stts_layer_scale_res_bwd(_ptr(xc), _ptr(gc), _ptr(dy), B, L, C, _ptr(dx), _ptr(dg), _ptr(ws),
+                                             int(nb), _stream()), "stts_layer_scale_res_bwd")
+        return dx, (gy if nr else None), (dg.reshape(ctx.g_shape) if dg is not None else None)
+
+
+def layer_scale_res(x, r, gamma):
+    return _LayerScaleResFn.apply(x, r, gamma)
+
+
+class _ISTFTHeadFn(torch.autograd.Function):
+    """ISTFTHead after its Linear + ISTFT 'same' (vocos.py:282-296, :190-232): h [B, F, n_fft + 2] -> audio [B, F hop].
+    The window is a buffer (no gradient)."""
+
+    @staticmethod
+    def forward(ctx, h, window, n_fft, hop):
+        _require_device()
+        B, F, W = h.shape
+        if W != n_fft + 2 or window.numel() != n_fft:
+            raise ValueError(f"ISTFT head: h {tuple(h.shape)}, window {tuple(window.shape)} for n_fft {n_fft}")
+        hc, wc = _f32(h), _f32(window)
+        nb = _tl().stts_istft_head_workspace_bytes(B, F, n_fft, hop)
+        check(int(nb) if nb < 0 else 0, "stts_istft_head_workspace_bytes")
+        ws = _ws(nb, h.device)
+        y = torch.empty(B, F * hop, dtype=torch.float32, device=h.device)
+        check(_tl().stts_istft_head_fwd(_ptr(hc), _ptr(wc), B, F, n_fft, hop, _ptr(y), _ptr(ws), int(nb), _stream()),
+              "stts_istft_head_fwd")
+        ctx.save_for_backward(hc, wc)
+        ctx.geo = (n_fft, hop)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        hc, wc = ctx.saved_tensors
+        n_fft, hop = ctx.geo
+        B, F, _ = hc.shape
+        dy = _f32(gy)
+        dh = torch.empty_like(hc)
+        check(_tl().stts_istft_head_bwd(_ptr(hc), _ptr(wc), _ptr(dy), B, F, n_fft, hop, _ptr(dh), None, 0, _stream()),
+              "stts_istft_head_bwd")
+        return dh, None, None, None
+
+
+def istft_head(h, window, n_fft, hop):
+    return _ISTFTHeadFn.apply(h, window, int(n_fft), int(hop))
+
+
+def convnext_block_frames(m, x, s, dtype="fp32"):
+    """ConvNeXtBlock.forward (vocos.py:56-69) on frames x [B, L, C] for a module with the reference's parameter
+    layout (stts2_mi355x.vocos.ConvNeXtBlock): dwconv -> AdaIN1d -> pwconv1 -> GELU -> pwconv2 -> x + gamma * (.)."""
+    h = dwconv1d_frames(x, m.dwconv.weight, m.dwconv.bias)
+    h = adain_act(h, s, m.norm.fc.weight, m.norm.fc.bias, None, ACT_NONE)
+    h = conv1d_frames(h, m.pwconv1.weight.unsqueeze(-1), m.pwconv1.bias, dtype=dtype)  # nn.Linear as [N][K][1]
+    h = gelu(h)
+    h = conv1d_frames(h, m.pwconv2.weight.unsqueeze(-1), m.pwconv2.bias, dtype=dtype)
+    return layer_scale_res(h, x, m.gamma)
+
+
+def vocos_generator_forward(g, x, s, dtype="fp32"):
+    """Generator.forward (vocos.py:157-162) + ISTFTHead.forward (:271-296) on frames x [B, F, dim] -> [B, F hop]."""
+    from .texttrain import layer_norm_act  # stts_row_norm / stts_row_norm_bwd, mode 0 (texttrain imports this module)
+    for blk in g.convnext:
+        x = convnext_block_frames(blk, x, s, dtype)
+    ln = g.final_layer_norm
+    x = layer_norm_act(x, ln.weight, ln.bias, ln.eps, None, None)  # eps 1e-6, no LeakyReLU, no row mask
+    head = g.stft
+    n_fft, hop = int(head.n_fft), int(head.hop_length)
+    W, b = head.out.weight, head.out.bias
+    # the head Linear has n_fft + 2 output columns (1202 / 1026): zero weight rows pad them to the conv engines'
+    # 16-column multiple and the output is sliced, so autograd returns the gradients of the real rows
+    padn = -W.shape[0] % 16
+    if padn:
+        W = torch.cat([W, W.new_zeros(padn, W.shape[1])])
+        b = torch.cat([b, b.new_zeros(padn)])
+    h = conv1d_frames(x, W.unsqueeze(-1), b, dtype=dtype)[..., :n_fft + 2]
+    return istft_head(h, head.istft.window, n_fft, hop)
+
+
+def vocos_decoder_forward(dec, asr, F0_curve, N, s, dtype="fp32"):
+    """Decoder.forward (vocos.py:392-421) with autograd through HIP kernels: asr [B, 512, T], F0_curve and N [B, 2T],
+    s [B, style_dim] -> [B, 1, 2T hop].  `dec` is stts2_mi355x.vocos.Decoder; in .train() mode the F0 / N smoothing
+    of :393-401 is applied first (Python's random, as the reference).  The convs and GEMMs take `dtype` (fp32, bf16,
+    bf16x3) as for HiFi-GAN; the depthwise conv, GELU, layer scale and ISTFT head are fp32 frames in all three."""
+    _require_device()
+    if dtype not in _DT:
+        raise ValueError(f"dtype {dtype!r}: expected one of {list(_DT)}")
+    if dec.training:
+        F0_curve, N = train_smooth(F0_curve, N)
+    x = _decoder_frontend(dec, asr, F0_curve, N, s, dtype)
+    return vocos_generator_forward(dec.generator, x, s, dtype).unsqueeze(1)
 
 
 # ---------------------------------------------------------------------- discriminators

@@ -41,6 +41,9 @@ and the noise seed (stts_source_fwd_seed_dev, written before each replay).  Call
 kernels' one-time setup), call 2 records the graph and replays it, later calls copy their inputs into the graph's
 static buffers and replay.  The returned losses are the graph's static outputs (overwritten by the next replay) and
 the input gradients land on `static_inputs`; optimizer state["step"] follows after AdamW.sync_steps().
+The decoder may be a vocos.Decoder (its `noise=` / `seed=` keywords are accepted and ignored: Vocos has no source);
+that step runs eagerly only: `graph=True` raises NotImplementedError for it (the hipGraph capture of the Vocos step
+is not built).
 `freeze_d_in_g` (default) turns off requires_grad of the discriminator parameters
 during the G step: the reference computes those gradients and discards them (its next iteration starts
 with zero_grad before they are used), so skipping them changes no update.
@@ -75,6 +78,8 @@ class TrainStep:
         self.gl, self.dl = GeneratorLoss(mpd, msd), DiscriminatorLoss(mpd, msd)
         self.stft_loss = MultiResolutionSTFTLoss()
         self.graph = bool(graph)
+        if self.graph and getattr(decoder, "decoder_type", None) == "vocos":
+            raise NotImplementedError("TrainStep(graph=True) records the HiFi-GAN step; a Vocos decoder trains eagerly")
         self._graph, self._calls, self.static_inputs, self._static_out = None, 0, None, None
         mk = lambda m, lr: AdamW(m.parameters(), lr=lr, weight_decay=1e-4, betas=(0.0, 0.99), eps=1e-9,  # noqa: E731
                                  capturable=self.graph)

@@ -6,7 +6,9 @@ names and state-dict keys (the front-end's weight-norm layers use
 torch.nn.utils.parametrizations.weight_norm there: `<layer>.parametrizations.weight.original0` = g,
 `original1` = v; the ISTFT window is the `generator.stft.istft.window` buffer), so a Vocos
 checkpoint loads unchanged.  `forward(asr, F0_curve, N, s)` runs the whole decoder as HIP kernels
-through the C-ABI (`include/stts2.h`, STTS_KIND_VOCOS, `stts_decoder_fwd`); no PyTorch compute.
+through the C-ABI: under torch.no_grad() the fused plan (`include/stts2.h`, STTS_KIND_VOCOS,
+`stts_decoder_fwd`), with autograd the layer pairs of `training.vocos_decoder_forward`
+(`include/stts2_train.h`); no PyTorch compute.
 """
 from __future__ import annotations
 
@@ -117,7 +119,7 @@ class Generator(nn.Module):
 
 
 class Decoder(nn.Module):
-    """reference vocos.py:364-421; forward = HIP decoder (eval semantics)."""
+    """reference vocos.py:364-421; forward = HIP decoder (inference engine, or the autograd path when training)."""
 
     decoder_type = "vocos"
 
@@ -149,9 +151,20 @@ class Decoder(nn.Module):
             self._engine = DecoderEngine(self, dtype=dtype)
         return self._engine
 
-    def forward(self, asr, F0_curve, N, s, dtype: str = "fp32"):
+    def forward(self, asr, F0_curve, N, s, noise=None, seed=None, utt_offset: int = 0, dtype: str = "fp32"):
         """asr [B,512,T], F0_curve [B,2T], N [B,2T], s [B,style_dim] -> [B,1,2T*hop] (float32).
-        The Vocos decoder has no harmonic source, so it draws no noise."""
-        from .engine import forward_only
-        forward_only(self, "vocos.Decoder")
+
+        With grad mode on and a parameter or an input requiring grad the call runs the autograd path
+        (training.vocos_decoder_forward: forward and backward as HIP kernels); otherwise the fused inference
+        engine.  In .train() mode the F0 / N smoothing of vocos.py:393-401 is applied first on either path.
+        The Vocos decoder has no harmonic source, so it draws no noise: `noise`, `seed` and `utt_offset` are
+        accepted (so that TrainStep calls every decoder alike) and ignored."""
+        from . import training
+        if torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters()) or any(
+                isinstance(t, torch.Tensor) and t.requires_grad for t in (asr, F0_curve, N, s))):
+            return training.vocos_decoder_forward(self, asr, F0_curve, N, s, dtype=dtype)
+        if self.training:
+            dev = torch.device("cuda", torch.cuda.current_device())
+            F0_curve, N = training.train_smooth(torch.as_tensor(F0_curve).to(dev, torch.float32),
+                                                torch.as_tensor(N).to(dev, torch.float32))
         return self.engine(dtype).forward(asr, F0_curve, N, s)

@@ -1,0 +1,79 @@
+"""One fine-tune step with the Vocos decoder (n_fft 1200, hop 300) on one MI355X at the config-5 shape:
+B = 2 segments of 155 asr frames = 93,000 samples, TrainStep (decoder forward, D step, G step, AdamW), eager.
+
+    python tools/bench_vocos_train.py [--steps 10] [--warmup 3] [--dtypes bf16,fp32] [--out profiles/vocos_train_bench.json]
+
+Prints one JSON line per dtype (median of hipEvent-timed steps, wall and host issue time) and, with --out, writes
+the list to that file.  Inputs are synthetic and resident in HBM, formula weights.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "styletts2-lite_amd"), os.path.join(ROOT, "tests")]
+import torch  # noqa: E402
+
+
+def run(dtype, B, T, n_fft, hop, steps, warmup):
+    from helpers import fill_module
+    from stts2_mi355x import synth
+    from stts2_mi355x.discriminators import MultiPeriodDiscriminator, MultiResSpecDiscriminator
+    from stts2_mi355x.trainstep import TrainStep
+    from stts2_mi355x.vocos import Decoder
+    dec = fill_module(Decoder(dim_in=512, style_dim=128, dim_out=80, intermediate_dim=1536, num_layers=8,
+                              gen_istft_n_fft=n_fft, gen_istft_hop_size=hop)).cuda().eval()
+    mpd = fill_module(MultiPeriodDiscriminator(), "mpd.").cuda().train()
+    msd = fill_module(MultiResSpecDiscriminator(), "msd.").cuda().train()
+    ins = [torch.from_numpy(a).cuda().requires_grad_(True) for a in synth.decoder_inputs(B, T, tag="train")]
+    wav = torch.from_numpy(synth.waves(B, 2 * T * hop, 7)).cuda()
+    step = TrainStep(dec, mpd, msd, dtype=dtype)
+    for i in range(max(warmup, 1)):
+        step(*ins, wav, seed=100 + i)
+    torch.cuda.synchronize()
+    ev, host = [], []
+    t0 = time.perf_counter()
+    for i in range(steps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        h0 = time.perf_counter()
+        out = step(*ins, wav, seed=1000 + i)
+        host.append((time.perf_counter() - h0) * 1e3)
+        b.record()
+        ev.append((a, b))
+    torch.cuda.synchronize()
+    wall = (time.perf_counter() - t0) / steps * 1e3
+    ms = statistics.median(x.elapsed_time(y) for x, y in ev)
+    return {"metric": "vocos train step (eager)", "dtype": dtype, "B": B, "T_frames": T, "n_fft": n_fft, "hop": hop,
+            "samples_per_utt": 2 * T * hop, "ms_per_step_median": round(ms, 2), "ms_per_step_wall": round(wall, 2),
+            "host_ms_per_step": round(statistics.median(host), 2), "steps": steps, "warmup": warmup,
+            "losses": {k: float(out[k]) for k in ("d_loss", "loss_mel", "loss_gen_all")},
+            "max_mem_gb": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--dtypes", default="bf16,fp32")
+    ap.add_argument("--B", type=int, default=2)
+    ap.add_argument("--T", type=int, default=155)
+    ap.add_argument("--n-fft", type=int, default=1200)
+    ap.add_argument("--hop", type=int, default=300)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    rows = []
+    for dt in a.dtypes.split(","):
+        rows.append(run(dt, a.B, a.T, a.n_fft, a.hop, a.steps, a.warmup))
+        print(json.dumps(rows[-1]), flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(rows, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
