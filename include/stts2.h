@@ -379,7 +379,10 @@ const char* stts_error_string(int code);
 #define STTS_ABI_VERSION 5
 int stts_abi_version(void);
 
-/* Engine options (process-wide, take effect on the next launch):
+/* Engine options (process-wide, take effect on the next launch).  The keys are addressed by number (tools/ab_engine.py,
+ * the recorded profiles), so a key is never renumbered.  Keys 3, 9, 26 and 28 are retired (options whose engines lost
+ * their A/B runs and were removed) and are never reused: stts_set_option and stts_get_option return
+ * STTS_EINVAL for them, as for an unknown key.
  *   STTS_OPT_RESCONV  1 (default) = the specialised resblock conv engine serves the bf16
  *                     C = 32 / 64 dilated convs; 0 = the general implicit-GEMM engine serves them
  *                     (A/B measurement and cross-checking of the two engines). */
@@ -387,10 +390,7 @@ int stts_abi_version(void);
 /*   STTS_OPT_GRID_CAP n > 0 caps the persistent conv grids at n workgroups (testing: forces many
  *                     tiles and utterance changes per workgroup); 0 (default) = one per CU. */
 #define STTS_OPT_GRID_CAP 2
-/*   STTS_OPT_RESFUSED 1 = bf16 AdaINResBlock1 iterations at C = 32 (and C = 64, K = 3) run as a
- *                     statistics-only conv1 launch + one fused conv1 -> conv2 launch (resfused.hip);
- *                     0 (default) = two conv launches per iteration (A/B, cross-checking). */
-#define STTS_OPT_RESFUSED 3
+/*   (3: retired) */
 /*   STTS_OPT_DEBUG    bit mask skipping phases of the resblock engine (1 prologue math, 2 MFMAs,
  *                     4 epilogue) for timing experiments; outputs are WRONG while set.  0 = off. */
 #define STTS_OPT_DEBUG 4
@@ -413,10 +413,7 @@ int stts_abi_version(void);
 /*   STTS_OPT_HEAD     1 (default) = the HiFi-GAN output head (Snake -> conv_post -> tanh) runs as one
  *                     streaming pass (head.hip); 0 = on the igemm engine (A/B). */
 #define STTS_OPT_HEAD 8
-/*   STTS_OPT_SKEW     0 (default) = every bigconv2 workgroup starts at once; v != 0: half of them
- *                     (odd ones for v > 0, the grid's second half for v < 0) start |v| x 1024 cycles
- *                     late, so two workgroups sharing a CU run out of phase (A/B experiments). */
-#define STTS_OPT_SKEW 9
+/*   (9: retired) */
 /*   STTS_OPT_FRONT    1 (default) = the decoder front-end's k3 AdainResBlk1d convs (C_out 1024 / 512)
  *                     run on the bigconv2 engine when the launch has at least half as many tiles as
  *                     CUs (else igemm: small batches); 2 = bigconv2 at any size (tests); 0 = igemm. */
@@ -430,12 +427,12 @@ int stts_abi_version(void);
  *                     (fp32 slice partials in the plan workspace, summed in slice order; B = 1 decoder
  *                     5.70 -> 4.92 ms); 0 = off. */
 #define STTS_OPT_SPLITK 12
-/*   STTS_OPT_EXP      bit mask of engine experiments under A/B (tools/ab_engine.py); 0 = the measured
- *                     defaults.  1: bigconv2 static MFMA priority for the second half of the waves;
- *                     2: bigconv2 residual epilogue in one load batch; 4: resconv residual prefetched
- *                     one tile ahead; 32: ups[2] (N = 192) on 4-wave bigconv2 blocks of one output phase per tile
- *                     part instead of 12-wave blocks of all three phases; 64: the accuracy mode's ups[3] with one
- *                     output phase per tile part instead of both. */
+/*   STTS_OPT_EXP      bit mask selecting an older kernel layout that computes the same bits as the default one: the
+ *                     independent references of three bitwise tests; 0 (default) = the measured defaults.
+ *                     32: ups[2] (N = 192) on 4-wave bigconv2 blocks of one output phase per tile part instead of
+ *                     12-wave blocks of all three phases; 64: the accuracy mode's ups[3] with one output phase per
+ *                     tile part instead of both; 32768: every resconv launch with the previous tile's epilogue
+ *                     interleaved into the MFMA loop (else STTS_OPT_RCPP 3's launches only).  Other bits are ignored. */
 #define STTS_OPT_EXP 13
 /*   STTS_OPT_UPS      1 = the HiFi-GAN ups[0] / ups[1] / ups[2] polyphase upsamplers (N = 2,560 / 640 / 192) on the
  *                     bigconv2 engine and ups[3] on resconv (default); 2 = ups[2] on conv1d_igemm (A/B); 0 = all on
@@ -488,19 +485,13 @@ int stts_abi_version(void);
  *                     groups, 3 MFMAs a product); 3 / 4 = the same on 4- / 8-wave blocks everywhere; 0 = the split
  *                     implicit-GEMM engine (A/B). */
 #define STTS_OPT_BIGSPLIT 25
-/*   STTS_OPT_BIGLA 1 = the bigconv2 engine's 3-tap (and ups[0]'s 2-tap) launches on 8-wave blocks DMA each window
- *                     two groups ahead into a third LDS buffer, so it lands before its transform; 0 (default) = one
- *                     group ahead (two buffers).  Bit-identical outputs; measured neutral (A/B). */
-#define STTS_OPT_BIGLA 26
+/*   (26: retired) */
 /*   STTS_OPT_BIG64 bit 1 = the accuracy mode's C = 64 resblock convs on the bigconv2 engine with 128-frame wave
  *                     slices (instead of the two-pass split resblock engine); bit 2 = the bf16 C = 64 resblock convs on it
  *                     too (instead of resconv); bit 4 = on 4-wave blocks, two per CU (else 8-wave); bit 8 = the accuracy mode's C = 32
  *                     convs as well (64-frame slices; slower than the split resblock engine, A/B); default 5; 0 = off. */
 #define STTS_OPT_BIG64 27
-/*   STTS_OPT_BIG3  bit mask: 1 = the bf16 C = 128 / 256 resblock convs, 2 = the front-end k3 convs, 4 = ups[0] / ups[1] run
- *                     on the v3 engine (64-channel x 128-frame wave tiles, block-shared weight chunks; bitwise equal to
- *                     bigconv2); 8 = its C = 128 convs on 8-wave blocks (else two 4-wave blocks per CU); 0 = off. */
-#define STTS_OPT_BIG3 28
+/*   (28: retired) */
 /*   STTS_OPT_SEGPART 1 (default) = batches of 32 k utterances split every persistent conv launch into utterance-relative
  *                     tile ranges (kernels.h tile_range), so each workgroup's fp32 partial statistics, and with them every
  *                     output bit, do not depend on the batch size: an N-rank job (256 / N utterances a rank) decodes
@@ -512,7 +503,7 @@ int stts_abi_version(void);
  *                     4-wave blocks per CU (168 VGPRs, three waves per SIMD: 5-6 % faster per launch, round 6); 0 = two. */
 #define STTS_OPT_RCOCC 30
 int stts_set_option(int key, int value);
-/* Current value of an option (STTS_EINVAL for an unknown key). */
+/* Current value of an option (STTS_EINVAL for an unknown or retired key). */
 int stts_get_option(int key);
 /* Diagnostics (not a product path): a device buffer of >= 16 uint64 that instrumented engines add
  * per-phase s_memtime cycle sums into (bigconv2.hip: set STTS_OPT_DEBUG bit 64); NULL = off. */
@@ -523,7 +514,7 @@ int stts_set_debug_buffer(void* buf);
 int stts_profile_enable(int on);
 int stts_profile_read(double* total_ms, long long* launches, double* alg_flops, double* alg_bytes);
 /* Launch i of the timed region: shape = {B, rows, N, Cin, taps, dilation, Lout,
- * res | acc<<1 | engine<<4} with engine 0 = conv1d_igemm, 1 = resconv, 2 = bigconv, 3 = resfused,
+ * res | acc<<1 | engine<<4} with engine 0 = conv1d_igemm, 1 = resconv, 2 = bigconv, 3 = retired (the fused resblock engine),
  * ms_flops_bytes = {hipEvent ms, algorithmic flops, algorithmic bytes}. */
 int stts_profile_launch(long long i, int* shape, double* ms_flops_bytes);
 

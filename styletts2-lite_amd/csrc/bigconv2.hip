@@ -47,17 +47,13 @@ namespace {
 // OFS: the second half of the waves (wu >= NW / 2) runs one group behind the first (3 window buffers), so the
 // two waves of each SIMD reach their tile epilogues one group apart and one's epilogue runs beside the other's
 // MFMAs (STTS_OPT_BIGCONV 5 / 6)
-// LA: window lookahead 2 (3 window buffers): slot sl DMAs window sl + 2 instead of sl + 1, so a window lands a whole
-// group (K taps) before its transform instead of K - 1 or K - 2 taps.  For K <= 3 those 1-2 taps (~1.5 us) are
-// about one LDS-DMA latency under load, so the transform waited on the DMA (STTS_OPT_BIGLA)
 // NF: 32-frame accumulator fragments per wave (8: 256 frames; 4: 128 frames, for C = 64, whose two 32-channel
 // output blocks leave 4 frame slices per 8-wave tile: 512-frame windows instead of 1,024)
 template <int C, int NW, int K, int DIL, int PRO = PK_SNAKE, int CINP = C, bool UPS = false, int CO = C, bool OFS = false,
-          bool LA = false, int NF = 8, int NCB = 0>
+          int NF = 8, int NCB = 0>
 struct B2 {
   static_assert(NF == 8 || NF == 4 || NF == 2, "fragments per wave");
-  static_assert(!(OFS && LA), "one use of the third window buffer");
-  static constexpr int NXB = (OFS || LA) ? 3 : 2;  // window buffers
+  static constexpr int NXB = OFS ? 3 : 2;  // window buffers
   static constexpr int NCOEF = PRO == PK_SNAKE ? 5 : 2;  // coefficient rows per input channel
   // 32-channel output blocks per block tile (NCB: a smaller count, for column counts no power of two divides: ups[2])
   static constexpr int NCBW = NCB ? NCB : ((C / 32 < NW) ? C / 32 : NW);
@@ -100,11 +96,10 @@ struct B2 {
 
 // SEG: several tile ranges per workgroup (segmented partition, p.seg > 0, with fewer workgroups than segments); the
 // plain instantiation runs the one-range code (a range loop in every launch measured ~0.5 % of the step)
-template <int C, int NW, int K, int DIL, bool RES, bool ACC, int PRO = PK_SNAKE, int CINP = C, bool EPI1 = false,
-          bool UPS = false, int CO = C, bool OFS = false, bool SP = false, bool LA = false, int NF = 8, int NCB = 0,
-          bool SEG = false>
+template <int C, int NW, int K, int DIL, bool RES, bool ACC, int PRO = PK_SNAKE, int CINP = C, bool UPS = false,
+          int CO = C, bool OFS = false, bool SP = false, int NF = 8, int NCB = 0, bool SEG = false>
 __global__ void __launch_bounds__(64 * NW, NW == 12 ? 3 : 2) k_bigconv2(const ConvParams p) {
-  using G = B2<C, NW, K, DIL, PRO, CINP, UPS, CO, OFS, LA, NF, NCB>;
+  using G = B2<C, NW, K, DIL, PRO, CINP, UPS, CO, OFS, NF, NCB>;
   constexpr int FW = 32 * NF;  // frames per wave
   constexpr int NXB = G::NXB;
   constexpr int TM = G::TM, NWIN = G::NWIN, PD = G::PD, RS = G::RS, NCH = G::NCH, NCO = G::NCO;
@@ -160,13 +155,6 @@ __global__ void __launch_bounds__(64 * NW, NW == 12 ? 3 : 2) k_bigconv2(const Co
   };
   const unsigned long long t_start = t_mark;
 
-  // STTS_OPT_SKEW: half the workgroups start |skew| x 1024 cycles late (odd ones for skew > 0, the
-  // second half of the grid for skew < 0), so that two workgroups sharing a CU run out of phase
-  if (p.skew != 0 && (p.skew > 0 ? (blockIdx.x & 1) != 0 : blockIdx.x >= gridDim.x / 2)) {
-    const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-    const unsigned long long d = (unsigned long long)(p.skew > 0 ? p.skew : -p.skew) * 1024ull;
-    while (__builtin_amdgcn_s_memtime() - t0 < d) __builtin_amdgcn_s_sleep(8);
-  }
   for (int i = tid; i < CO; i += NT) bias_s[i] = p.bias ? p.bias[i] : 0.f;
   for (int i = tid; i < G::FH * G::NPH * 2 * CO; i += NT) st_lds[i] = 0.f;
 
@@ -445,11 +433,9 @@ __global__ void __launch_bounds__(64 * NW, NW == 12 ? 3 : 2) k_bigconv2(const Co
     // pending it would wait vmcnt(0) at every use); the empty asm fences pin the issue order.
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), expcnt / lgkmcnt unconstrained
     lap(7);
-    // (EPI1: a residual-only epilogue loads all 8 fragments in one batch, into the registers the dead
-    // tap fragments held: one load latency per tile instead of two; STTS_OPT_EXP bit 2)
     // (SP: fp32 residual / running-sum rows, 64 B per fragment: 4 fragments a batch with a residual only, 2 with a
     // residual and a running sum)
-    constexpr int NB0 = SP ? (RES ? (ACC ? 4 : 2) : 1) : ((RES && !(EPI1 && !ACC)) ? 2 : 1);
+    constexpr int NB0 = SP ? (RES ? (ACC ? 4 : 2) : 1) : (RES ? 2 : 1);
     constexpr int NB = NB0 * NF / 8 > 0 ? NB0 * NF / 8 : 1, FB = NF / NB;  // (the same batch size at NF = 4)
     uint4 rl[FB][NU], al[FB][NU];
     auto unpack16 = [&](const uint4 (&u)[NU], float (&o)[16]) __attribute__((always_inline)) {
@@ -613,13 +599,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 12 ? 3 : 2) k_bigconv2(const Co
   issue_x(0, 0, cur.b, cur.mt);
 #pragma unroll
   for (int s = 0; s < PD; ++s) issue_w(s, 0, cur.ch, s);
-  if constexpr (LA) {  // window 1 as well (slot 0 DMAs window 2)
-    const GCur c1 = NGG > 1 ? advance(cur) : cur;
-    issue_x(1, c1.gi, c1.b, c1.mt);
-    vm_wait<2 * PD + NWIN>();  // this wave's window DMA of group 0 landed
-  } else {
-    vm_wait<2 * PD>();
-  }
+  vm_wait<2 * PD>();
   transform(0, 0, cur.b, cur.mt);
 
   // the accumulators of tile tt start at the bias.  Set right after the previous tile's epilogue
@@ -639,9 +619,6 @@ __global__ void __launch_bounds__(64 * NW, NW == 12 ? 3 : 2) k_bigconv2(const Co
   // DMAs and transforms its share of window sl + 1; a wave computes group gw = sl - off (OFS: off = 1 for the
   // second half of the waves, which so runs one slot behind on window buffers sl - 1; one extra slot at the end)
   init_acc(cur.ch);
-  // STTS_OPT_EXP bit 1: static MFMA-issue priority for the second-dispatched half of the waves
-  // (MI355X_MICROARCH.md, two waves per SIMD, item 4)
-  if ((p.exp & 1) && wu >= NW / 2) __builtin_amdgcn_s_setprio(1);
   const int off = (OFS && wu >= NW / 2) ? 1 : 0;
   constexpr int XS = OFS ? 1 : 0;  // extra slots
   GCur prv = cur;  // the group of the previous slot (the lagging half's compute group)
@@ -678,12 +655,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 12 ? 3 : 2) k_bigconv2(const Co
     // (the extra slot re-issues a harmless window DMA, untransformed and never read, so that every slot's
     // vmcnt waits count the same younger operations)
     const bool windows = sl < NGG;
-    if constexpr (LA) {  // buffer (sl+2) % 3, last read in slot sl - 1 (before this slot's barrier)
-      const GCur nn = sl + 2 < NGG ? advance(nxt) : nxt;
-      issue_x(sl + 2, nn.gi, nn.b, nn.mt);
-    } else {
-      issue_x(sl + 1, nxt.gi, nxt.b, nxt.mt);  // buffer (sl+1) % NXB, last read NXB - 1 slots ago
-    }
+    issue_x(sl + 1, nxt.gi, nxt.b, nxt.mt);  // buffer (sl+1) % NXB, last read NXB - 1 slots ago
     if (!active) {  // the lagging half's first slot: only its share of window 1
       if (windows) {
         vm_wait<0>();
@@ -778,24 +750,8 @@ __global__ void __launch_bounds__(64 * NW, NW == 12 ? 3 : 2) k_bigconv2(const Co
       constexpr int TX2 = (NW == 8) ? K - 2 : K - 1;
       if (windows && ((t == TX && (NW != 8 || wu < 4)) || (t == TX2 && NW == 8 && wu >= 4))) {
         lap(6);
-        if constexpr (LA) {
-          // window sl + 1 was DMA'd at the start of slot sl - 1 (slot 0: in the prologue).  Younger: slot sl - 1's K
-          // weight steps (and its epilogue's NST stores when it closed a tile), window sl + 2's DMA, and this slot's
-          // weight steps of taps 0..t
-          constexpr int Y1 = NWIN + 2 * K, Y2 = NWIN + 2 * (K - 1);  // t = K - 1 / K - 2
-          if (t == K - 1) {
-            if (sl == 0) vm_wait<Y1>();
-            else if (post_epi) vm_wait<Y1 + 2 * K + NST>();
-            else vm_wait<Y1 + 2 * K>();
-          } else {
-            if (sl == 0) vm_wait<Y2>();
-            else if (post_epi) vm_wait<Y2 + 2 * K + NST>();
-            else vm_wait<Y2 + 2 * K>();
-          }
-        } else {
-          if (t == K - 1) vm_wait<2 * K>();
-          else vm_wait<2 * (K - 1)>();
-        }
+        if (t == K - 1) vm_wait<2 * K>();
+        else vm_wait<2 * (K - 1)>();
         lap(1);
         transform(sl + 1, nxt.gi, nxt.b, nxt.mt);
         lap(3);
@@ -822,10 +778,10 @@ __global__ void __launch_bounds__(64 * NW, NW == 12 ? 3 : 2) k_bigconv2(const Co
   }  // tile ranges
 }
 
-template <int C, int NW, int K, int DIL, bool RES, bool ACC, int PRO = PK_SNAKE, int CINP = C, bool EPI1 = false,
-          bool UPS = false, int CO = C, bool OFS = false, bool SP = false, bool LA = false, int NF = 8, int NCB = 0>
+template <int C, int NW, int K, int DIL, bool RES, bool ACC, int PRO = PK_SNAKE, int CINP = C, bool UPS = false,
+          int CO = C, bool OFS = false, bool SP = false, int NF = 8, int NCB = 0>
 int launch_b2(const ConvParams& p, hipStream_t stream) {
-  using G = B2<C, NW, K, DIL, PRO, CINP, UPS, CO, OFS, LA, NF, NCB>;
+  using G = B2<C, NW, K, DIL, PRO, CINP, UPS, CO, OFS, NF, NCB>;
   static int ncu = 0;
   if (!ncu) {
     int dev = 0;
@@ -842,48 +798,40 @@ int launch_b2(const ConvParams& p, hipStream_t stream) {
   // tile count), so only a launch with more segments than workgroups needs the range loop
   const bool segk = seg > 0 && grid < (long long)p.B * seg;
   q.seg = segk ? seg : 0;
-  auto kern = segk ? k_bigconv2<C, NW, K, DIL, RES, ACC, PRO, CINP, EPI1, UPS, CO, OFS, SP, LA, NF, NCB, true>
-                   : k_bigconv2<C, NW, K, DIL, RES, ACC, PRO, CINP, EPI1, UPS, CO, OFS, SP, LA, NF, NCB, false>;
+  auto kern = segk ? k_bigconv2<C, NW, K, DIL, RES, ACC, PRO, CINP, UPS, CO, OFS, SP, NF, NCB, true>
+                   : k_bigconv2<C, NW, K, DIL, RES, ACC, PRO, CINP, UPS, CO, OFS, SP, NF, NCB, false>;
   static bool attr[2] = {false, false};
   if (!attr[segk]) {
     ST_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
     attr[segk] = true;
   }
-  q.skew = g_opt_skew;
-  q.exp = g_opt_exp;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * NW), G::LDS, stream, q);
   return (int)hipGetLastError();
 }
 
-template <int C, int NW, int K, bool OFS = false, bool SP = false, bool LA = false, int NF = 8>
+template <int C, int NW, int K, bool OFS = false, bool SP = false, int NF = 8>
 int launch_b2_k(const ConvParams& p, hipStream_t s) {
   constexpr bool F = false;
   if (!p.res) {  // conv1 of an iteration: dilation 1 / 3 / 5, no residual
     if (p.accb) return ST_EINVAL;
     switch (p.dil) {
-      case 1: return launch_b2<C, NW, K, 1, F, F, PK_SNAKE, C, F, F, C, OFS, SP, LA, NF>(p, s);
-      case 3: return launch_b2<C, NW, K, 3, F, F, PK_SNAKE, C, F, F, C, OFS, SP, LA, NF>(p, s);
-      case 5: return launch_b2<C, NW, K, 5, F, F, PK_SNAKE, C, F, F, C, OFS, SP, LA, NF>(p, s);
+      case 1: return launch_b2<C, NW, K, 1, F, F, PK_SNAKE, C, F, C, OFS, SP, NF>(p, s);
+      case 3: return launch_b2<C, NW, K, 3, F, F, PK_SNAKE, C, F, C, OFS, SP, NF>(p, s);
+      case 5: return launch_b2<C, NW, K, 5, F, F, PK_SNAKE, C, F, C, OFS, SP, NF>(p, s);
       default: return ST_EINVAL;
     }
   }
   if (p.dil != 1) return ST_EINVAL;  // conv2: dilation 1, residual, optionally the resblock sum
-  if (p.accb) return launch_b2<C, NW, K, 1, true, true, PK_SNAKE, C, F, F, C, OFS, SP, LA, NF>(p, s);
-  if constexpr (!OFS && !SP && !LA && NF == 8)
-    if (g_opt_exp & 2) return launch_b2<C, NW, K, 1, true, false, PK_SNAKE, C, true>(p, s);
-  return launch_b2<C, NW, K, 1, true, F, PK_SNAKE, C, F, F, C, OFS, SP, LA, NF>(p, s);
+  if (p.accb) return launch_b2<C, NW, K, 1, true, true, PK_SNAKE, C, F, C, OFS, SP, NF>(p, s);
+  return launch_b2<C, NW, K, 1, true, F, PK_SNAKE, C, F, C, OFS, SP, NF>(p, s);
 }
 
 template <int C, int NW, bool OFS = false, bool SP = false, int NF = 8>
 int launch_b2_c(const ConvParams& p, hipStream_t s) {
   switch (p.KS) {
-    case 3:
-      if constexpr (NW == 8 && !OFS && C >= 256)  // the window lookahead (B2::LA) where it fits: 8-wave blocks, 3 taps
-        // (C = 128: its 512-row windows leave no room for a third buffer)
-        if (g_opt_bigla) return launch_b2_k<C, NW, 3, OFS, SP, true>(p, s);
-      return launch_b2_k<C, NW, 3, OFS, SP, false, NF>(p, s);
-    case 7: return launch_b2_k<C, NW, 7, OFS, SP, false, NF>(p, s);
-    case 11: return launch_b2_k<C, NW, 11, OFS, SP, false, NF>(p, s);
+    case 3: return launch_b2_k<C, NW, 3, OFS, SP, NF>(p, s);
+    case 7: return launch_b2_k<C, NW, 7, OFS, SP, NF>(p, s);
+    case 11: return launch_b2_k<C, NW, 11, OFS, SP, NF>(p, s);
     default: return ST_EINVAL;
   }
 }
@@ -893,11 +841,7 @@ int launch_b2_c(const ConvParams& p, hipStream_t s) {
 // STTS_OPT_BIGCONV: 1 = bigconv.hip (v1, A/B); 2 = this engine, 8-wave blocks (one per CU);
 // 3 = this engine, 4-wave blocks (two per CU, C = 256 split into two 128-channel output parts)
 int g_opt_bigconv = 2;
-// STTS_OPT_BIGLA: the 3-tap / 2-tap 8-wave launches with the window lookahead (B2::LA).  Off: measured neutral
-// (profiles/r05_ab_bigla.txt: C = 256 k3 156 -> 161 us, the front-end and ups[0] within 2 %), so the window DMA's
-// latency is not what the 3-tap launches wait on
-int g_opt_bigla = 0;
-int g_opt_skew = 0;
+// STTS_OPT_EXP: the reference layouts of three bitwise tests (bits 32 / 64 here, 32768 in resconv.hip)
 int g_opt_exp = 0;
 
 bool st_bigconv2_eligible(const ConvParams& p) {
@@ -941,17 +885,6 @@ bool st_front_eligible(const ConvParams& p, int dtype) {
 }
 
 int st_bigconv2_front(const ConvParams& p, hipStream_t s) {
-  if (g_opt_big3 & 2) return st_bigconv3_front(p, s);
-  constexpr bool F = false;
-  if (g_opt_bigla) {
-    if (p.Cout == 1024)
-      return p.res ? launch_b2<1024, 8, 3, 1, true, F, PK_LRELU, FE_CINP, F, F, 1024, F, F, true>(p, s)
-                   : launch_b2<1024, 8, 3, 1, false, F, PK_LRELU, FE_CINP, F, F, 1024, F, F, true>(p, s);
-    if (p.Cout == 512)
-      return p.res ? launch_b2<512, 8, 3, 1, true, F, PK_LRELU, FE_CINP, F, F, 512, F, F, true>(p, s)
-                   : launch_b2<512, 8, 3, 1, false, F, PK_LRELU, FE_CINP, F, F, 512, F, F, true>(p, s);
-    return ST_EINVAL;
-  }
   if (p.Cout == 1024)
     return p.res ? launch_b2<1024, 8, 3, 1, true, false, PK_LRELU, FE_CINP>(p, s)
                  : launch_b2<1024, 8, 3, 1, false, false, PK_LRELU, FE_CINP>(p, s);
@@ -999,18 +932,15 @@ bool st_ups_eligible(const ConvParams& p, int dtype) {
 }
 
 int st_bigconv2_ups(const ConvParams& p, hipStream_t s) {
-  if ((g_opt_big3 & 4) && ((p.N == 2560 && p.Cout == 256) || (p.N == 640 && p.Cout == 128))) return st_bigconv3_ups(p, s);
-  if (p.N == 2560 && p.Cout == 256)
-    return g_opt_bigla ? launch_b2<2560, 8, 2, 1, true, false, PK_SNAKE, 512, false, true, 256, false, false, true>(p, s)
-                       : launch_b2<2560, 8, 2, 1, true, false, PK_SNAKE, 512, false, true, 256>(p, s);
-  if (p.N == 640 && p.Cout == 128) return launch_b2<640, 4, 2, 1, true, false, PK_SNAKE, 256, false, true, 128>(p, s);
+  if (p.N == 2560 && p.Cout == 256) return launch_b2<2560, 8, 2, 1, true, false, PK_SNAKE, 512, true, 256>(p, s);
+  if (p.N == 640 && p.Cout == 128) return launch_b2<640, 4, 2, 1, true, false, PK_SNAKE, 256, true, 128>(p, s);
   // ups[2]: 12-wave blocks (three per SIMD) of all 6 output blocks (the 3 phases) x 2 frame slices of 128 frames, so each
   // window is DMA'd and transformed once instead of once per phase: 668 -> 479 us (profiles/r05_ab_ups12.txt).
   // STTS_OPT_EXP bit 32: 4-wave blocks of 2 output blocks (one 64-column phase per tile part), as before (A/B)
   if (p.N == 192 && p.Cout == 64) {
     if (g_opt_exp & 32)
-      return launch_b2<192, 4, 2, 1, true, false, PK_SNAKE, 128, false, true, 64, false, false, false, 4, 2>(p, s);
-    return launch_b2<192, 12, 2, 1, true, false, PK_SNAKE, 128, false, true, 64, false, false, false, 4, 6>(p, s);
+      return launch_b2<192, 4, 2, 1, true, false, PK_SNAKE, 128, true, 64, false, false, 4, 2>(p, s);
+    return launch_b2<192, 12, 2, 1, true, false, PK_SNAKE, 128, true, 64, false, false, 4, 6>(p, s);
   }
   return ST_EINVAL;
 }
@@ -1069,28 +999,28 @@ int st_bigsplit(const ConvParams& p, hipStream_t s) {
   // (profiles/r05_ab_ups12.txt; STTS_OPT_EXP bit 64: one phase per tile part, as before)
   if (g_opt_ups == 1 && st_resconv_ups_eligible(p, ST_BF16)) {
     if (g_opt_exp & 64)
-      return launch_b2<64, 4, 2, 1, true, false, PK_SNAKE, 64, false, true, 32, false, true, false, 2, 1>(p, s);
-    return launch_b2<64, 4, 2, 1, true, false, PK_SNAKE, 64, false, true, 32, false, true, false, 2, 2>(p, s);
+      return launch_b2<64, 4, 2, 1, true, false, PK_SNAKE, 64, true, 32, false, true, 2, 1>(p, s);
+    return launch_b2<64, 4, 2, 1, true, false, PK_SNAKE, 64, true, 32, false, true, 2, 2>(p, s);
   }
   if (st_ups_eligible(p, ST_BF16)) {
     if (p.N == 2560 && p.Cout == 256)
-      return launch_b2<2560, 8, 2, 1, true, false, PK_SNAKE, 512, false, true, 256, false, true>(p, s);
+      return launch_b2<2560, 8, 2, 1, true, false, PK_SNAKE, 512, true, 256, false, true>(p, s);
     if (p.N == 640 && p.Cout == 128)
-      return launch_b2<640, 4, 2, 1, true, false, PK_SNAKE, 256, false, true, 128, false, true>(p, s);
+      return launch_b2<640, 4, 2, 1, true, false, PK_SNAKE, 256, true, 128, false, true>(p, s);
     if (p.N == 192 && p.Cout == 64) {  // (12-wave blocks as bf16: 1167 -> 926 us; bit 32: the 4-wave blocks)
       if (g_opt_exp & 32)
-        return launch_b2<192, 4, 2, 1, true, false, PK_SNAKE, 128, false, true, 64, false, true, false, 4, 2>(p, s);
-      return launch_b2<192, 12, 2, 1, true, false, PK_SNAKE, 128, false, true, 64, false, true, false, 4, 6>(p, s);
+        return launch_b2<192, 4, 2, 1, true, false, PK_SNAKE, 128, true, 64, false, true, 4, 2>(p, s);
+      return launch_b2<192, 12, 2, 1, true, false, PK_SNAKE, 128, true, 64, false, true, 4, 6>(p, s);
     }
     return ST_EINVAL;
   }
   if (st_front_eligible(p, ST_BF16)) {
     if (p.Cout == 1024)
-      return p.res ? launch_b2<1024, 8, 3, 1, true, false, PK_LRELU, FE_CINP, false, false, 1024, false, true>(p, s)
-                   : launch_b2<1024, 8, 3, 1, false, false, PK_LRELU, FE_CINP, false, false, 1024, false, true>(p, s);
+      return p.res ? launch_b2<1024, 8, 3, 1, true, false, PK_LRELU, FE_CINP, false, 1024, false, true>(p, s)
+                   : launch_b2<1024, 8, 3, 1, false, false, PK_LRELU, FE_CINP, false, 1024, false, true>(p, s);
     if (p.Cout == 512)
-      return p.res ? launch_b2<512, 8, 3, 1, true, false, PK_LRELU, FE_CINP, false, false, 512, false, true>(p, s)
-                   : launch_b2<512, 8, 3, 1, false, false, PK_LRELU, FE_CINP, false, false, 512, false, true>(p, s);
+      return p.res ? launch_b2<512, 8, 3, 1, true, false, PK_LRELU, FE_CINP, false, 512, false, true>(p, s)
+                   : launch_b2<512, 8, 3, 1, false, false, PK_LRELU, FE_CINP, false, 512, false, true>(p, s);
     return ST_EINVAL;
   }
   // resblock convs: 4-wave blocks (two per CU) where the bf16 engine takes them (few tiles, C = 128 k7 / k11)

@@ -874,10 +874,9 @@ int launch_typed(const ConvParams& p, hipStream_t stream) {
   }
   if (p.epi_tanh) return ST_EINVAL;  // tanh only on narrow heads
   // stride 2 with N <= 32 (the MSD (3, 9) layers of the training step, N = 32): BM 128 x BN 32, every
-  // column live, instead of the 64 x 128 tile with three quarters of its columns idle (STTS_OPT_EXP 1024:
-  // the old tile, for A/B)
+  // column live, instead of the 64 x 128 tile with three quarters of its columns idle
   if constexpr (ConvCfg<T, MT, 1, 1, 1, 1, SPF>::LOWP) {
-    if (p.stride == 2 && p.N <= 32 && !(g_opt_exp & 1024)) return launch_cfg<T, MT, 4, 1, 1, 1, false, SPF>(p, stream);
+    if (p.stride == 2 && p.N <= 32) return launch_cfg<T, MT, 4, 1, 1, 1, false, SPF>(p, stream);
   }
   if (p.stride > 1) return launch_cfg<T, MT, 2, 2, 1, 2, false, SPF>(p, stream);  // BM 64 x BN 128 (short window)
   if (p.N > 64 && g_opt_small_tiles) {
@@ -905,7 +904,6 @@ int launch_typed(const ConvParams& p, hipStream_t stream) {
 
 int g_opt_resconv = 1;
 int g_opt_small_tiles = 1;
-int g_opt_resfused = 0;
 int g_opt_grid_cap = 0;
 int g_opt_segpart = 1;
 

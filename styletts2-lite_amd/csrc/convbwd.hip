@@ -386,16 +386,10 @@ int wgw_slices(int B, int Lq, int Cin, int Cout, int K) {
   const long long units = (long long)B * ((Lq + WGW_CH - 1) / WGW_CH);
   // ~256 workgroups: the fp32 partials (S x Cout x Cin x K) and their reduction scale with the slice count,
   // and at config-5 shapes 256 measured 30-50 % faster than 1,024 on the dw call (wgrad + reduction,
-  // profiles/r03_ab_wgrad_slices.txt).  STTS_OPT_EXP bit 128 / 256 / 512: 512 / 1,024 / 128 (A/B).
-  const long long target = (g_opt_exp & 512) ? 128 : (g_opt_exp & 256) ? 1024 : (g_opt_exp & 128) ? 512 : 256;
-  long long S = (target + tiles - 1) / tiles;
-  // (STTS_OPT_EXP bit 2048, off: few-input-channel convs over many rows get one slice per 16 chunks while the
-  // partials stay under 32 MB; on the MSD first layer, Cin = 3 over 1.9 M rows, it measured slower, dw 0.59 ->
-  // 0.75 ms, profiles/r03_ab_msd_conv.txt)
-  if (Cin <= 16 && (g_opt_exp & 2048)) {
-    const long long per = std::max<long long>(1, (long long)Cout * Cin * K * 4);
-    S = std::max(S, std::min<long long>(units / 16, (32ll << 20) / per));
-  }
+  // profiles/r03_ab_wgrad_slices.txt; 128 / 512 / 1,024 were the other targets tried).  More slices for
+  // few-input-channel convs over many rows measured slower too (the MSD first layer, Cin = 3 over 1.9 M rows:
+  // dw 0.59 -> 0.75 ms, profiles/r03_ab_msd_conv.txt)
+  long long S = (256 + tiles - 1) / tiles;
   S = std::min<long long>(S, std::max<long long>(1, units / 2));
   return (int)std::max<long long>(1, std::min<long long>(S, 4096));
 }
@@ -768,7 +762,7 @@ int run_engine(int dtype, const Geo& g, bool fwd, const float* xf, const float* 
 template <int K, int ST = 1>
 void launch_wgw(const Geo& g, const float* x, const float* dy, float* part, int S, hipStream_t s, int txH) {
   const int ntci = (g.Cin + 63) / 64, ntco = (g.Cout + 63) / 64;
-  if (g.Cout <= 32 && !(g_opt_exp & 4096))  // (STTS_OPT_EXP bit 4096: every tap on the fi = 0 waves, A/B)
+  if (g.Cout <= 32)
     hipLaunchKernelGGL((k_wgrad_bf16w<K, ST, true>), dim3(ntco * ntci, S), dim3(256), 0, s, x, dy, g.Lin, g.Cin, g.Lq,
                        g.Cout, g.dil, g.pad, g.B, S, ntci, part, txH);
   else

@@ -52,8 +52,6 @@ struct ConvParams {
   // from the statistics (keeps the padded image borders zero); zc_period = 0 disables.
   int zc_period, zc_valid;
   int dbg;         // phase-skipping timing knob (STTS_OPT_DEBUG; results are wrong when set)
-  int skew;        // bigconv2 start skew of half the workgroups (STTS_OPT_SKEW, set by the launcher)
-  int exp;         // experiment bits (STTS_OPT_EXP, set by the launchers that read them)
   unsigned long long* stamps;  // diagnostics: per-phase s_memtime cycle sums (stts_set_debug_buffer), or null
   int tg;          // taps per staged weight group (set by the launcher)
   int cps;         // 32-channel chunks per pipeline step, 1 or 2 (set by the launcher)
@@ -104,8 +102,9 @@ __device__ __forceinline__ double* stats_slot(const ConvParams& p, int g) {
 int st_stats_fold(double* stats, int B, int ld, int C, int slots, long long slot_bs, hipStream_t s);
 // n fixed-point statistics entries (ST_W words) -> n (sum, sumsq) fp64 pairs (test hooks)
 int st_stats_decode(const double* fx, long long n, double* out, hipStream_t s);
-// which engine st_conv1d routes p to (profiling records; bench.py names the dominant kernel)
-enum { ST_ENGINE_IGEMM = 0, ST_ENGINE_RESCONV = 1, ST_ENGINE_BIGCONV = 2, ST_ENGINE_RESFUSED = 3, ST_ENGINE_HEAD = 4,
+// which engine st_conv1d routes p to (profiling records; bench.py names the dominant kernel).  3 is retired (the
+// fused resblock engine) and is not reused: recorded profiles carry these values
+enum { ST_ENGINE_IGEMM = 0, ST_ENGINE_RESCONV = 1, ST_ENGINE_BIGCONV = 2, ST_ENGINE_HEAD = 4,
        ST_ENGINE_PW = 5, ST_ENGINE_RESSPLIT = 6, ST_ENGINE_BIGSPLIT = 7 };
 // split-operand (ST_SPLIT) resblock convs, C = 32 / 64 (ressplit.hip; C = 64 needs p.splitk_ws >= B Lq 64 floats)
 bool st_ressplit_eligible(const ConvParams& p, int dtype);
@@ -116,7 +115,6 @@ extern int g_opt_ressplit;
 bool st_bigsplit_eligible(const ConvParams& p, int dtype);
 int st_bigsplit(const ConvParams& p, hipStream_t stream);
 extern int g_opt_bigsplit;  // STTS_OPT_BIGSPLIT
-extern int g_opt_bigla;     // STTS_OPT_BIGLA
 // C = 64 resblock convs on the bigconv2 engine with 128-frame wave slices (bf16 and / or ST_SPLIT, STTS_OPT_BIG64)
 bool st_big64_eligible(const ConvParams& p, int dtype);
 int st_big64(const ConvParams& p, int dtype, hipStream_t stream);
@@ -143,8 +141,7 @@ int st_bigconv(const ConvParams& p, hipStream_t stream);
 bool st_bigconv2_eligible(const ConvParams& p);
 int st_bigconv2(const ConvParams& p, hipStream_t stream);
 extern int g_opt_bigconv;
-extern int g_opt_skew;  // STTS_OPT_SKEW (bigconv2.hip)
-extern int g_opt_exp;   // STTS_OPT_EXP (bigconv2.hip, resconv.hip): A/B experiment bits
+extern int g_opt_exp;   // STTS_OPT_EXP (bigconv2.hip, resconv.hip): the reference layouts of three bitwise tests
 // the decoder front-end's k3 AdainResBlk1d convs on the bigconv2 engine (STTS_OPT_FRONT)
 bool st_front_eligible(const ConvParams& p, int dtype);
 int st_bigconv2_front(const ConvParams& p, hipStream_t stream);
@@ -157,12 +154,6 @@ extern int g_opt_cout1;  // STTS_OPT_COUT1 (convbwd.hip)
 extern int g_opt_plainrc;  // resconv.hip: prologue-free C = 32 / 64 convs (training step) on resconv (STTS_OPT_PLAINRC)  // convbwd.hip: bf16 weight gradient of stride-1 convs on k_wgrad_bf16w (STTS_OPT_WGRAD)
 bool st_ups_eligible(const ConvParams& p, int dtype);
 int st_bigconv2_ups(const ConvParams& p, hipStream_t stream);
-// engine v3 of the same work (bigconv3.hip: 64-channel x 128-frame wave tiles, block-shared weight chunks), routed
-// by STTS_OPT_BIG3 bits from st_bigconv / st_bigconv2_front / st_bigconv2_ups
-int st_bigconv3(const ConvParams& p, hipStream_t stream);
-int st_bigconv3_front(const ConvParams& p, hipStream_t stream);
-int st_bigconv3_ups(const ConvParams& p, hipStream_t stream);
-extern int g_opt_big3;
 extern int g_opt_front;
 // HiFi-GAN output head (head.hip): Snake -> conv_post (C -> 1, 7 taps) -> tanh as one streaming pass;
 // st_conv1d routes eligible launches to it while g_opt_head != 0
@@ -178,41 +169,6 @@ bool st_pw_split_eligible(const ConvParams& p, int dtype);
 extern int g_opt_splitk;  // STTS_OPT_SPLITK
 int st_pw_split(const ConvParams& p, hipStream_t stream);
 extern int g_opt_pw;
-
-// fused AdaINResBlock1 iteration (resfused.hip): bf16, C = 32 (K = 3/7/11) or 64 (K = 3): a statistics pass
-// (stats_only) then the fused conv1 -> AdaIN2 -> Snake2 -> conv2 -> + x pass.
-//   y = conv2(Snake2(AdaIN2(conv1(Snake1(AdaIN1(x)))))) + x     (hifigan.py:65-74)
-// pro2.stats must already hold the statistics of conv1's output (a statistics-only conv1 launch).
-// y must not alias x (neighbouring tiles read x halos).  accb != null: y = (accb + .) / acc_div
-// (acc_div 0 = no division) and no statistics; otherwise statistics of y when stats != null.
-struct ResFusedParams {
-  const void* x;
-  long long x_bs;
-  int x_ld, B, L, C, K, dil;
-  const void* w1;
-  const float* b1;
-  Prologue pro1;
-  const void* w2;
-  const float* b2;
-  Prologue pro2;
-  void* y;
-  long long y_bs;
-  int y_ld;
-  const void* accb;
-  long long acc_bs;
-  int acc_ld;
-  float acc_div;
-  double* stats;
-  int stats_ld;
-  int stats_slots;  // as ConvParams::stats_slots
-  long long stats_slot_bs;
-  int stats_only;  // 1: conv1 only over the output frames, its statistics into `stats` (no y, no conv2)
-  int dbg;  // phase-skipping timing bits (STTS_OPT_DEBUG, set by st_resfused): 1 prologue math, 2 MFMAs,
-            // 4 residual loads + stores, 8 window loads (results are wrong when set)
-};
-extern int g_opt_resfused;
-bool st_resfused_eligible(int C, int K, int dil, int dtype);
-int st_resfused(const ResFusedParams& p, hipStream_t stream);
 
 // ---------------------------------------------------------------- misc kernels
 // src [B][C][L] fp32 (torch NCL) -> dst frames [B][L][ld] at channel offset c0; optional stats.

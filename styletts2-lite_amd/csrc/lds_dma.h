@@ -1,4 +1,4 @@
-// Device helpers shared by the LDS-DMA conv engines (bigconv2.hip, bigconv3.hip): counted vmcnt waits, the raw
+// Device helpers of the LDS-DMA conv engine (bigconv2.hip): counted vmcnt waits, the raw
 // workgroup barrier that keeps LDS-DMAs in flight, LDS accesses the compiler cannot see (so it does not drain the
 // in-flight DMAs before them), bf16 packing.
 #pragma once

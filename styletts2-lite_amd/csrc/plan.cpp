@@ -757,24 +757,6 @@ int conv_run(Ctx& c, ConvParams& p) {
   return 0;
 }
 
-int resfused_run(Ctx& c, ResFusedParams& p) {
-  if (c.dry) return 0;
-  const bool prof = g_prof.on;
-  if (prof) ST_CHECK(prof_begin(c));
-  p.stats_slots = p.stats ? c.slots : 1;
-  p.stats_slot_bs = (long long)c.B * p.stats_ld * ST_W;
-  ST_CHECK(st_resfused(p, c.s));
-  if (prof) {
-    // algorithmic work: the statistics pass = conv1 over x (x read once); the fused pass = both convs, x once
-    // (window + residual), the running sum, y
-    const double fl = (p.stats_only ? 2.0 : 4.0) * p.B * (double)p.L * p.C * p.C * p.K;
-    const double by = (double)p.B * p.L * p.C * (p.stats_only ? 1.0 : 2.0 + (p.accb ? 1.0 : 0.0)) * c.esz;
-    const int flags = (p.stats_only ? 0 : 1) | (p.accb ? 2 : 0) | (ST_ENGINE_RESFUSED << 4);
-    ST_CHECK(prof_end(c, {p.B, p.L, p.C, p.C, p.K, p.dil, p.L, flags}, fl, by));
-  }
-  return 0;
-}
-
 // AdainResBlk1d forward (hifigan.py:390-403).  x frames (ld, L); output into y at channel c0.
 int adain_blk(Ctx& c, const AdainBlk& k, const Buf& x, int xc0, const double* st_x, int st_x_ld, const Buf& y,
               int yc0, double* st_y, int st_y_ld, Buf& H1, Buf& SC, Buf& POOL) {
@@ -853,59 +835,6 @@ int resblock1(Ctx& c, const ResBlock1& rb, const Buf& X, const double* st_x, Buf
   const int L = X.L, C = rb.C;
   const Buf* xc = &X;
   const double* st_c = st_x;
-  if (st_resfused_eligible(C, rb.K, 1, c.dtype)) {
-    // fused iterations (resfused.hip): a statistics pass of conv1, then one launch for
-    // conv1 -> AdaIN2 -> Snake2 -> conv2 -> +x.  Outputs ping-pong X -> R -> XT -> R (or ACC):
-    // a fused launch reads its input's halos, so it cannot write in place.
-    Buf* outs[3] = {&R, &XT, &R};
-    for (int d = 0; d < 3; ++d) {
-      if (!st_resfused_eligible(C, rb.K, rb.dil[d], c.dtype)) return ST_EINVAL;
-      double* st_xt = c.stat(C);
-      ResFusedParams f;
-      memset(&f, 0, sizeof(f));
-      f.x = xc->p;
-      f.x_bs = xc->bs;
-      f.x_ld = xc->ld;
-      f.B = c.B;
-      f.L = L;
-      f.C = C;
-      f.K = rb.K;
-      f.dil = rb.dil[d];
-      f.w1 = c.wpk(rb.c1[d]);
-      f.b1 = c.P(rb.c1[d].bias);
-      f.pro1 = pro_adain(c, rb.a1[d], st_c, C, L, PRO_SNAKE, rb.al1[d], 0.f);
-      f.stats_only = 1;
-      f.stats = st_xt;
-      f.stats_ld = C;
-      RUN(resfused_run(c, f));
-      f.stats_only = 0;
-      f.stats = nullptr;
-      f.w2 = c.wpk(rb.c2[d]);
-      f.b2 = c.P(rb.c2[d].bias);
-      f.pro2 = pro_adain(c, rb.a2[d], st_xt, C, L, PRO_SNAKE, rb.al2[d], 0.f);
-      const bool final = d == 2;
-      const Buf* y = (final && ro != RO_PLAIN) ? ACC : outs[d];
-      f.y = y->p;
-      f.y_bs = y->bs;
-      f.y_ld = y->ld;
-      if (final && ro != RO_PLAIN) {
-        if (ro != RO_ACC_FIRST) {
-          f.accb = ACC->p;
-          f.acc_bs = ACC->bs;
-          f.acc_ld = ACC->ld;
-          if (ro == RO_ACC_LAST) f.acc_div = (float)nk;
-        }
-      } else if (!final) {
-        double* st_r = c.stat(C);
-        f.stats = st_r;
-        f.stats_ld = C;
-        st_c = st_r;
-      }
-      RUN(resfused_run(c, f));
-      xc = outs[d];
-    }
-    return 0;
-  }
   for (int d = 0; d < 3; ++d) {
     double* st_xt = c.stat(C);
     {
@@ -2015,13 +1944,11 @@ int stts_set_option(int key, int value) {
   switch (key) {
     case STTS_OPT_RESCONV: g_opt_resconv = value != 0; return 0;
     case STTS_OPT_GRID_CAP: g_opt_grid_cap = value > 0 ? value : 0; return 0;
-    case STTS_OPT_RESFUSED: g_opt_resfused = value != 0; return 0;
     case STTS_OPT_DEBUG: g_opt_debug = value; return 0;
     case STTS_OPT_STATS_SLOTS: g_opt_stats_slots = value > 0 ? value : 0; return 0;
     case STTS_OPT_SMALL_TILES: g_opt_small_tiles = value != 0; return 0;
     case STTS_OPT_BIGCONV: g_opt_bigconv = (value >= 1 && value <= 5) ? value : 2; return 0;
     case STTS_OPT_HEAD: g_opt_head = value ? 1 : 0; return 0;
-    case STTS_OPT_SKEW: g_opt_skew = value; return 0;
     case STTS_OPT_FRONT: g_opt_front = (value >= 0 && value <= 2) ? value : 1; return 0;
     case STTS_OPT_PW: g_opt_pw = (value >= 0 && value <= 2) ? value : 1; return 0;
     case STTS_OPT_SPLITK: g_opt_splitk = value ? 1 : 0; return 0;
@@ -2033,9 +1960,7 @@ int stts_set_option(int key, int value) {
     case STTS_OPT_RCPP: g_opt_rcpp = (value >= 0 && value <= 3) ? value : 1; return 0;
     case STTS_OPT_RESSPLIT: g_opt_ressplit = value ? 1 : 0; return 0;
     case STTS_OPT_BIGSPLIT: g_opt_bigsplit = value; return 0;
-    case STTS_OPT_BIGLA: g_opt_bigla = value; return 0;
     case STTS_OPT_BIG64: g_opt_big64 = value; return 0;
-    case STTS_OPT_BIG3: g_opt_big3 = value; return 0;
     case STTS_OPT_SEGPART: g_opt_segpart = value; return 0;
     case STTS_OPT_RCOCC: g_opt_rcocc = value; return 0;
     case STTS_OPT_BF16F: g_opt_bf16f = value ? 1 : 0; return 0;
@@ -2049,7 +1974,7 @@ int stts_set_option(int key, int value) {
       if (value < 0) return ST_EINVAL;
       g_opt_nbranch = value;
       return 0;
-    default: return ST_EINVAL;
+    default: return ST_EINVAL;  // (unknown and retired keys)
   }
 }
 
@@ -2062,13 +1987,11 @@ int stts_get_option(int key) {
   switch (key) {
     case STTS_OPT_RESCONV: return g_opt_resconv;
     case STTS_OPT_GRID_CAP: return g_opt_grid_cap;
-    case STTS_OPT_RESFUSED: return g_opt_resfused;
     case STTS_OPT_DEBUG: return g_opt_debug;
     case STTS_OPT_STATS_SLOTS: return g_opt_stats_slots;
     case STTS_OPT_SMALL_TILES: return g_opt_small_tiles;
     case STTS_OPT_BIGCONV: return g_opt_bigconv;
     case STTS_OPT_HEAD: return g_opt_head;
-    case STTS_OPT_SKEW: return g_opt_skew;
     case STTS_OPT_FRONT: return g_opt_front;
     case STTS_OPT_PW: return g_opt_pw;
     case STTS_OPT_SPLITK: return g_opt_splitk;
@@ -2080,9 +2003,7 @@ int stts_get_option(int key) {
     case STTS_OPT_RCPP: return g_opt_rcpp;
     case STTS_OPT_RESSPLIT: return g_opt_ressplit;
     case STTS_OPT_BIGSPLIT: return g_opt_bigsplit;
-    case STTS_OPT_BIGLA: return g_opt_bigla;
     case STTS_OPT_BIG64: return g_opt_big64;
-    case STTS_OPT_BIG3: return g_opt_big3;
     case STTS_OPT_SEGPART: return g_opt_segpart;
     case STTS_OPT_RCOCC: return g_opt_rcocc;
     case STTS_OPT_BF16F: return g_opt_bf16f;

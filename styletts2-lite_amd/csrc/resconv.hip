@@ -68,17 +68,13 @@ __device__ __forceinline__ uint4 f32_to_bf8(const float* v) {
 
 // ACC: the launch adds the output into the resblock running sum (p.accb, p.acc_div) and keeps
 // no statistics (hifigan.py:336-342); otherwise statistics are kept when p.stats is set.
-// RPF: the residual / running-sum rows of tile t+1 are loaded during tile t (two register sets,
-// STTS_OPT_EXP bit 4), instead of at the start of the tile that consumes them
-// PF: window prefetch depth in tiles (2; 3 keeps a third raw window in flight: one block per CU at
-// C = 64 holds ~40 KB of loads in flight with two, below the ~70 KB an HBM-rate stream needs)
 // IL: the epilogue of tile t - 1 is issued inside tile t's MFMA loop (one basic block: branch-free, the stores go
 // through a buffer descriptor and rows that are not stored get an out-of-range offset), so its VALU work, residual
 // adds and stores fill the gaps between the MFMAs instead of running after them with the MFMA pipe idle
 // SEG: several tile ranges per workgroup (bigconv2.hip k_bigconv2: the plain instantiation runs one range)
 // MINB: blocks per CU the register allocation is held to (0: 8 / WAVES, two waves per SIMD)
-template <int C, int K, int DIL, int WAVES, int WAVES_N, bool ACC, bool RPF = false, int PF = 2, bool UPS = false,
-          bool IL = false, bool SEG = false, int MINB = 0>
+template <int C, int K, int DIL, int WAVES, int WAVES_N, bool ACC, bool UPS = false, bool IL = false, bool SEG = false,
+          int MINB = 0>
 __global__ void __launch_bounds__(64 * WAVES, MINB ? MINB : 8 / WAVES) k_resconv(const ConvParams p) {
   using G = RC<C, K, DIL, WAVES, WAVES_N, UPS>;
   constexpr int NT = G::NT, BM = G::BM, MT = G::MT, NTL = G::NTL, NCH = G::NCH, XP = G::XP, WP = G::WP;
@@ -237,7 +233,7 @@ __global__ void __launch_bounds__(64 * WAVES, MINB ? MINB : 8 / WAVES) k_resconv
   };
 
   int cur_b = -1;
-  auto step = [&](int t, uint4 (&pre)[MAXU], EpiRegs& er_, EpiRegs& er_next) __attribute__((always_inline)) {
+  auto step = [&](int t, uint4 (&pre)[MAXU], EpiRegs& er_) __attribute__((always_inline)) {
     const int b = t / ntm, mt = t - b * ntm;
     auto& rres = er_.rres;
     auto& racc = er_.racc;
@@ -263,17 +259,13 @@ __global__ void __launch_bounds__(64 * WAVES, MINB ? MINB : 8 / WAVES) k_resconv
       }
       cur_b = b;
     }
-    if constexpr (RPF) {
-      if (t + 1 < tend) issue_epi(t + 1, er_next);
-    } else {
-      issue_epi(t, er_);
-    }
+    issue_epi(t, er_);
     mark(0);
     __syncthreads();  // (A) coef / weights visible; every wave done reading Xs of the previous tile
     mark(1);
     transform(t, pre);
     mark(2);
-    if (t + PF < tend) issue(t + PF, pre);
+    if (t + 2 < tend) issue(t + 2, pre);
     mark(3);
     __syncthreads();  // (B) window complete
     mark(4);
@@ -353,7 +345,7 @@ __global__ void __launch_bounds__(64 * WAVES, MINB ? MINB : 8 / WAVES) k_resconv
             for (int r = 0; r < 16; ++r) v[r] *= osc;
           }
         }
-        if (valid) {  // y == null: statistics-only pass (resfused.hip needs conv1's statistics)
+        if (valid) {  // (y == null keeps the statistics and stores nothing; no plan launches it that way)
           if constexpr (ACC) {
             float r0[8], r1[8];
             bf8_to_f32(racc[mi][ni][0], r0);
@@ -450,7 +442,7 @@ __global__ void __launch_bounds__(64 * WAVES, MINB ? MINB : 8 / WAVES) k_resconv
     issue_epi(t > tbeg ? t - 1 : t, e_il);
     __syncthreads();  // (A)
     transform(t, pre);
-    if (t + PF < tend) issue(t + PF, pre);
+    if (t + 2 < tend) issue(t + 2, pre);
     __syncthreads();  // (B)
 #pragma unroll
     for (int mi = 0; mi < MT; ++mi)
@@ -531,22 +523,11 @@ __global__ void __launch_bounds__(64 * WAVES, MINB ? MINB : 8 / WAVES) k_resconv
   }
   uint4 preA[MAXU], preB[MAXU];
   EpiRegs eA, eB;
-  if constexpr (RPF) issue_epi(tbeg, eA);
   issue(tbeg, preA);
   if (tbeg + 1 < tend) issue(tbeg + 1, preB);
-  if constexpr (PF == 3) {
-    uint4 preC[MAXU];
-    if (tbeg + 2 < tend) issue(tbeg + 2, preC);
-    for (int t = tbeg; t < tend; t += 3) {
-      step(t, preA, eA, eB);
-      if (t + 1 < tend) step(t + 1, preB, eB, eA);
-      if (t + 2 < tend) step(t + 2, preC, eA, eB);
-    }
-  } else {
-    for (int t = tbeg; t < tend; t += 2) {
-      step(t, preA, eA, eB);
-      if (t + 1 < tend) step(t + 1, preB, eB, eA);
-    }
+  for (int t = tbeg; t < tend; t += 2) {
+    step(t, preA, eA);
+    if (t + 1 < tend) step(t + 1, preB, eB);
   }
   if (p.stats) flush(cur_b);
   cur_b = -1;  // (the range's statistics are out: the next range re-stages its coefficients, flushes nothing twice)
@@ -562,15 +543,14 @@ __global__ void __launch_bounds__(64 * WAVES, MINB ? MINB : 8 / WAVES) k_resconv
 
 int g_num_cu_rc = 0;
 
-// WV / WN: block shape override (0 = the default: 4 x 1 waves at C = 32, 8 x 2 at C = 64)
-template <int C, int K, int DIL, bool ACC, bool RPF = false, int PF = 2, bool UPS = false, int WV = 0, int WN = 0,
-          bool IL = false, int MINB = 0>
+// block shape: 4 x 1 waves at C = 32, 8 x 2 at C = 64
+template <int C, int K, int DIL, bool ACC, bool UPS = false, bool IL = false, int MINB = 0>
 int launch_rc(const ConvParams& p, hipStream_t stream) {
-  constexpr int WAVES = WV ? WV : C == 32 ? 4 : 8;
-  constexpr int WAVES_N = WN ? WN : C == 32 ? 1 : 2;
+  constexpr int WAVES = C == 32 ? 4 : 8;
+  constexpr int WAVES_N = C == 32 ? 1 : 2;
   using G = RC<C, K, DIL, WAVES, WAVES_N, UPS>;
-  auto kern0 = k_resconv<C, K, DIL, WAVES, WAVES_N, ACC, RPF, PF, UPS, IL, false, MINB>;
-  auto kern1 = k_resconv<C, K, DIL, WAVES, WAVES_N, ACC, RPF, PF, UPS, IL, true, MINB>;
+  auto kern0 = k_resconv<C, K, DIL, WAVES, WAVES_N, ACC, UPS, IL, false, MINB>;
+  auto kern1 = k_resconv<C, K, DIL, WAVES, WAVES_N, ACC, UPS, IL, true, MINB>;
   static bool attr = false;
   if (!attr) {
     ST_CHECK_HIP(hipFuncSetAttribute((const void*)kern0, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
@@ -940,10 +920,6 @@ int launch_pp(const ConvParams& p, hipStream_t stream) {
 
 template <int C, int K, int DIL>
 int launch_rc_a(const ConvParams& p, hipStream_t s) {
-  if constexpr (DIL == 1) {  // (the residual launches: conv2 of an iteration, dilation 1)
-    if ((g_opt_exp & 4) && (p.res || p.accb))
-      return p.accb ? launch_rc<C, K, 1, true, true>(p, s) : launch_rc<C, K, 1, false, true>(p, s);
-  }
   // STTS_OPT_RCPP: the two-group ping-pong kernel at C = 64 (1: residual / running-sum launches with K >= 7,
   // where the in-process A/B measured it faster, profiles/r03_ab_resconv_pp.txt; 2: every launch)
   // (3: those launches on the lock-step kernel with the interleaved epilogue instead, IL below)
@@ -951,34 +927,16 @@ int launch_rc_a(const ConvParams& p, hipStream_t s) {
     if (g_opt_rcpp == 2 || (g_opt_rcpp == 1 && K >= 7 && (p.res || p.accb)))
       return p.accb ? launch_pp<K, DIL, true>(p, s) : launch_pp<K, DIL, false>(p, s);
     if (g_opt_rcpp == 3 && K >= 7 && (p.res || p.accb))
-      return p.accb ? launch_rc<C, K, DIL, true, false, 2, false, 0, 0, true>(p, s)
-                    : launch_rc<C, K, DIL, false, false, 2, false, 0, 0, true>(p, s);
+      return p.accb ? launch_rc<C, K, DIL, true, false, true>(p, s) : launch_rc<C, K, DIL, false, false, true>(p, s);
   }
   // STTS_OPT_RCOCC: C = 32, K >= 7, no residual: registers held to three 4-wave blocks per CU (168 VGPRs, three waves
   // per SIMD; 5-6 % faster per launch, profiles/r06_ab_rc3b.txt; the k3 and residual launches measured 0-3 % slower)
   if constexpr (C == 32 && K >= 7) {
-    if (g_opt_rcocc && !p.res && !p.accb) return launch_rc<C, K, DIL, false, false, 2, false, 0, 0, false, 3>(p, s);
+    if (g_opt_rcocc && !p.res && !p.accb) return launch_rc<C, K, DIL, false, false, false, 3>(p, s);
   }
   // STTS_OPT_EXP bit 32768: the interleaved epilogue (IL)
   if (g_opt_exp & 32768)
-    return p.accb ? launch_rc<C, K, DIL, true, false, 2, false, 0, 0, true>(p, s)
-                  : launch_rc<C, K, DIL, false, false, 2, false, 0, 0, true>(p, s);
-  // STTS_OPT_EXP bit 262144 / 524288: C = 64 on 4-wave blocks (two or more per CU, each running its own tile loop,
-  // so one block's MFMAs overlap the other's memory / VALU phases): 4 x 2 waves of 64 frames x 32 channels (128-frame
-  // tiles) / 4 x 1 waves of 64 frames x 64 channels (256-frame tiles); bit 1048576 limits it to K = 3
-  if constexpr (C == 64) {
-    if ((g_opt_exp & (262144 | 524288)) && (K == 3 || !(g_opt_exp & 1048576))) {
-      if (g_opt_exp & 262144)
-        return p.accb ? launch_rc<C, K, DIL, true, false, 2, false, 4, 2>(p, s)
-                      : launch_rc<C, K, DIL, false, false, 2, false, 4, 2>(p, s);
-      return p.accb ? launch_rc<C, K, DIL, true, false, 2, false, 4, 1>(p, s)
-                    : launch_rc<C, K, DIL, false, false, 2, false, 4, 1>(p, s);
-    }
-  }
-  // STTS_OPT_EXP bit 8 / 16: window prefetch three tiles deep at C = 64 / C = 32 (register budget allows it:
-  // 231-249 VGPRs, occupancy unchanged)
-  if ((C == 64 && (g_opt_exp & 8)) || (C == 32 && (g_opt_exp & 16)))
-    return p.accb ? launch_rc<C, K, DIL, true, false, 3>(p, s) : launch_rc<C, K, DIL, false, false, 3>(p, s);
+    return p.accb ? launch_rc<C, K, DIL, true, false, true>(p, s) : launch_rc<C, K, DIL, false, false, true>(p, s);
   return p.accb ? launch_rc<C, K, DIL, true>(p, s) : launch_rc<C, K, DIL, false>(p, s);
 }
 
@@ -1040,5 +998,5 @@ bool st_resconv_ups_eligible(const ConvParams& p, int dtype) {
 }
 
 int st_resconv_ups(const ConvParams& p, hipStream_t stream) {
-  return launch_rc<64, 2, 1, false, false, 2, true>(p, stream);
+  return launch_rc<64, 2, 1, false, true>(p, stream);
 }

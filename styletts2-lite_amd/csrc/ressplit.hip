@@ -396,7 +396,7 @@ int launch_rs_pf(const ConvParams& p, hipStream_t stream) {
 template <int NOUT, int K, int DIL, int PASS, bool ACC>
 int launch_rs(const ConvParams& p, hipStream_t stream) {
   // (the prefetch only where the epilogue reads rows: a residual, a running sum or the pass-1 partials)
-  if (!(g_opt_exp & 16384) && (p.res || ACC || PASS == 2)) return launch_rs_pf<NOUT, K, DIL, PASS, ACC, true>(p, stream);
+  if (p.res || ACC || PASS == 2) return launch_rs_pf<NOUT, K, DIL, PASS, ACC, true>(p, stream);
   return launch_rs_pf<NOUT, K, DIL, PASS, ACC>(p, stream);
 }
 

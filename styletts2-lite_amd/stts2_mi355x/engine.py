@@ -168,9 +168,9 @@ def lib():
     return L
 
 
+# (keys 3, 9, 26 and 28 are retired and never reused: include/stts2.h)
 OPT_RESCONV = 1
 OPT_GRID_CAP = 2
-OPT_RESFUSED = 3
 OPT_DEBUG = 4
 OPT_STATS_SLOTS = 5
 
@@ -178,7 +178,6 @@ OPT_STATS_SLOTS = 5
 OPT_SMALL_TILES = 6
 OPT_BIGCONV = 7
 OPT_HEAD = 8
-OPT_SKEW = 9
 OPT_FRONT = 10
 OPT_PW = 11
 OPT_SPLITK = 12
@@ -195,17 +194,15 @@ OPT_COUT1 = 22
 OPT_BRANCHES = 23
 OPT_NBRANCH = 24
 OPT_BIGSPLIT = 25
-OPT_BIGLA = 26
 OPT_BIG64 = 27
-OPT_BIG3 = 28
 OPT_SEGPART = 29
 OPT_RCOCC = 30
 # the production defaults of every STTS_OPT_* (include/stts2.h)
-OPT_DEFAULTS = {OPT_RESCONV: 1, OPT_GRID_CAP: 0, OPT_RESFUSED: 0, OPT_DEBUG: 0, OPT_STATS_SLOTS: 0,
-                OPT_SMALL_TILES: 1, OPT_BIGCONV: 2, OPT_HEAD: 1, OPT_SKEW: 0, OPT_FRONT: 1, OPT_PW: 1, OPT_SPLITK: 1,
+OPT_DEFAULTS = {OPT_RESCONV: 1, OPT_GRID_CAP: 0, OPT_DEBUG: 0, OPT_STATS_SLOTS: 0,
+                OPT_SMALL_TILES: 1, OPT_BIGCONV: 2, OPT_HEAD: 1, OPT_FRONT: 1, OPT_PW: 1, OPT_SPLITK: 1,
                 OPT_EXP: 0, OPT_UPS: 1, OPT_WGRAD: 1, OPT_PLAINRC: 1, OPT_MSDFOLD: 1,
                 OPT_RCPP: 3, OPT_RESSPLIT: 1, OPT_BF16F: 0, OPT_YF32: 1, OPT_COUT1: 1, OPT_BRANCHES: 8, OPT_NBRANCH: 64,
-                OPT_BIGSPLIT: 1, OPT_BIGLA: 0, OPT_BIG64: 5, OPT_BIG3: 0, OPT_SEGPART: 1, OPT_RCOCC: 1}
+                OPT_BIGSPLIT: 1, OPT_BIG64: 5, OPT_SEGPART: 1, OPT_RCOCC: 1}
 # STTS_OPTS="KEY=VALUE,..." (A/B runs of whole suites): option values that replace the defaults for the process,
 # applied when the library loads and by reset_options()
 for _kv in filter(None, os.environ.get("STTS_OPTS", "").split(",")):
@@ -655,8 +652,8 @@ def profile_read():
     return {"ms": t.value, "launches": n.value, "flops": f.value, "bytes": b.value}
 
 
-ENGINE_KERNELS = ("conv1d_igemm_kernel", "k_resconv", "k_bigconv", "k_resfused", "k_conv_post",
-                  "k_pwgemm", "k_ressplit", "k_bigconv2[SP]")  # engine ids 0..7
+ENGINE_KERNELS = ("conv1d_igemm_kernel", "k_resconv", "k_bigconv", None, "k_conv_post",
+                  "k_pwgemm", "k_ressplit", "k_bigconv2[SP]")  # engine ids 0..7 (3: retired, no launch records it)
 
 
 def profile_launches():

@@ -164,6 +164,16 @@ def test_option_defaults_are_the_documented_ones():
     assert engine.lib().stts_get_option(999) < 0
 
 
+@pytest.mark.parametrize("key", [3, 9, 26, 28])
+def test_retired_option_keys_are_invalid(key):
+    """The retired STTS_OPT_* keys (include/stts2.h) are neither settable nor readable: STTS_EINVAL, no launch."""
+    from stts2_mi355x import engine
+    L = engine.lib()
+    assert key not in engine.OPT_DEFAULTS
+    assert L.stts_set_option(key, 1) == -1  # STTS_EINVAL
+    assert L.stts_get_option(key) == -1
+
+
 def test_bilstm_error_word_offset():
     """The BiLSTM error word lies inside the workspace, 8-byte aligned, before the exchange words."""
     from stts2_mi355x import prosody

@@ -55,7 +55,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=8)
     ap.add_argument("--skips", default="0,2")
-    ap.add_argument("--exp", type=int, default=0, help="STTS_OPT_EXP held during the run (8: 3-deep prefetch at C=64)")
+    ap.add_argument("--exp", type=int, default=0, help="STTS_OPT_EXP held during the run (32768: the interleaved epilogue on every launch)")
     a = ap.parse_args()
     torch.cuda.set_device(0)
     E.set_option(E.OPT_EXP, a.exp)
