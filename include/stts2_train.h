@@ -288,6 +288,41 @@ int stts_istft_head_fwd(const float* h, const float* window, int B, int F, int n
 int stts_istft_head_bwd(const float* h, const float* window, const float* dy, int B, int F, int n_fft, int hop,
                         float* dh, void* ws, long long ws_bytes, void* stream);
 
+/* ---- The iSTFTNet decoder under the G step (Modules/istftnet.py; csrc/istftnet_train.hip).  The CustomSTFT
+ * geometries accepted here: n_fft even, 4 <= n_fft <= 64, 1 <= hop <= n_fft, B <= 65535 (the reference's 20 / 5
+ * and the lite configurations; stts_model_create itself takes any positive pair for inference); otherwise
+ * STTS_EINVAL before any launch.  None of these entries needs a workspace. */
+
+/* CustomSTFT.transform (istftnet.py:207-243) of the harmonic source: wave [B][L], wr / wi = the module's
+ * weight_forward_real / _imag buffers [n_fft / 2 + 1][n_fft] -> out [B][F][n_fft + 2], F = L / hop + 1: replicate
+ * padding of n_fft / 2, mag = sqrt(re^2 + im^2 + 1e-14) in channels 0 .. n_fft / 2, then phase = atan2(im, re) with
+ * (im == 0 and re < 0) -> pi.  The reference runs it under no_grad (:544-550): there is no backward. */
+int stts_cstft_fwd(const float* wave, const float* wr, const float* wi, int B, int L, int n_fft, int hop, float* out,
+                   void* stream);
+
+/* The last stage's reflection_pad((1, 0)) fused with x + x_source (istftnet.py:558-561): x [B][L][C],
+ * src [B][L + 1][C] -> y [B][L + 1][C], y[0] = x[1] + src[0], y[t] = x[t - 1] + src[t].  L >= 2, any C (16-byte
+ * accesses when C % 4 == 0 and the pointers are 16-byte aligned).
+ * _bwd: dx [B][L][C] from dy [B][L + 1][C], dx[t] = dy[t + 1] + (t == 1 ? dy[0] : 0); the gradient of src is dy
+ * itself (not written). */
+int stts_padl_add_fwd(const float* x, const float* src, int B, int L, int C, float* y, void* stream);
+int stts_padl_add_bwd(const float* dy, int B, int L, int C, float* dx, void* stream);
+
+/* Generator.forward's head (istftnet.py:571-573) + CustomSTFT.inverse (:246-293): post [B][F][2 nb] (conv_post's
+ * output, nb = n_fft / 2 + 1), br / bi = the module's weight_backward_real / _imag buffers [nb][n_fft] ->
+ * audio [B][(F - 1) hop]:  mag = exp(post_k), ph = sin(post_{nb + k}), re = mag cos ph, im = mag sin ph,
+ * audio[j] = sum_t sum_k (re[t][k] br[k][p - t hop] - im[t][k] bi[k][p - t hop]) over 0 <= p - t hop < n_fft,
+ * p = j + n_fft / 2 (the trim); no window-sum normalisation, no clip.  F >= 2.  A workgroup owns 64 hops of
+ * samples: the transcendentals are evaluated once per (frame, bin) of its frames and halo in LDS.
+ * _bwd: dpost [B][F][2 nb] from dy [B][(F - 1) hop], the exact adjoint with the forward values recomputed from
+ * post (nothing else is saved): dre[t][k] = sum_n dy[t hop + n - n_fft / 2] br[k][n], dim = -sum_n dy[.] bi[k][n]
+ * (dy zero outside its range), dmag = dre cos ph + dim sin ph, dph = mag (dim cos ph - dre sin ph),
+ * dpost_k = dmag mag, dpost_{nb + k} = dph cos(post_{nb + k}).  The bases are buffers: no gradient. */
+int stts_cistft_head_fwd(const float* post, const float* br, const float* bi, int B, int F, int n_fft, int hop,
+                         float* audio, void* stream);
+int stts_cistft_head_bwd(const float* post, const float* br, const float* bi, const float* dy, int B, int F, int n_fft,
+                         int hop, float* dpost, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,9 @@
 """Drop-in `Modules.istftnet.Decoder` (reference Modules/istftnet.py:660-721).
 
 Same constructor signature and state-dict keys (including the CustomSTFT buffers
-`generator.stft.*`, reference istftnet.py:111-203), forward = HIP decoder.
+`generator.stft.*`, reference istftnet.py:111-203), forward = HIP decoder: under torch.no_grad() the
+fused plan (`include/stts2.h`, STTS_KIND_ISTFTNET, `stts_decoder_fwd`), with autograd the layer pairs of
+`training.istft_decoder_forward` (`include/stts2_train.h`); no PyTorch compute.
 """
 from __future__ import annotations
 
@@ -87,7 +89,7 @@ class Generator(nn.Module):
 
 
 class Decoder(nn.Module):
-    """reference istftnet.py:660-721; forward = HIP decoder (eval semantics)."""
+    """reference istftnet.py:660-721; forward = HIP decoder (inference engine, or the autograd path when training)."""
 
     decoder_type = "istftnet"
 
@@ -122,6 +124,20 @@ class Decoder(nn.Module):
         return self._engine
 
     def forward(self, asr, F0_curve, N, s, noise=None, seed=None, utt_offset: int = 0, dtype: str = "fp32"):
-        from .engine import forward_only
-        forward_only(self, "istftnet.Decoder")
+        """asr [B,512,T], F0_curve [B,2T], N [B,2T], s [B,style_dim] -> [B,1,2T*prod(rates)*hop] (float32).
+
+        With grad mode on and a parameter or an input requiring grad the call runs the autograd path
+        (training.istft_decoder_forward: forward and backward as HIP kernels); otherwise the fused inference
+        engine.  In .train() mode the F0 / N smoothing of istftnet.py:693-701 is applied first on either path.
+        `noise` / `seed` / `utt_offset` as for hifigan.Decoder.  generator.m_source.l_linear receives no gradient
+        (the reference computes the source under no_grad, :544-550)."""
+        from . import training
+        if torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters()) or any(
+                isinstance(t, torch.Tensor) and t.requires_grad for t in (asr, F0_curve, N, s))):
+            return training.istft_decoder_forward(self, asr, F0_curve, N, s, noise=noise, seed=seed,
+                                                  utt_offset=utt_offset, dtype=dtype)
+        if self.training:
+            dev = torch.device("cuda", torch.cuda.current_device())
+            F0_curve, N = training.train_smooth(torch.as_tensor(F0_curve).to(dev, torch.float32),
+                                                torch.as_tensor(N).to(dev, torch.float32))
         return self.engine(dtype).forward(asr, F0_curve, N, s, noise=noise, seed=seed, utt_offset=utt_offset)

@@ -97,6 +97,11 @@ def _tl():
         "stts_istft_head_workspace_bytes": ([i, i, i, i], ll),
         "stts_istft_head_fwd": ([vp, vp, i, i, i, i, vp, vp, ll, vp], i),
         "stts_istft_head_bwd": ([vp, vp, vp, i, i, i, i, vp, vp, ll, vp], i),
+        "stts_cstft_fwd": ([vp, vp, vp, i, i, i, i, vp, vp], i),
+        "stts_padl_add_fwd": ([vp, vp, i, i, i, vp, vp], i),
+        "stts_padl_add_bwd": ([vp, i, i, i, vp, vp], i),
+        "stts_cistft_head_fwd": ([vp, vp, vp, i, i, i, i, vp, vp], i),
+        "stts_cistft_head_bwd": ([vp, vp, vp, vp, i, i, i, i, vp, vp], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(L, name)
@@ -584,11 +589,28 @@ class AdainResBlk1d(nn.Module):
         return self.forward_frames(x.transpose(1, 2), s).transpose(1, 2)
 
 
-def adain_resblk1d_frames(m, x, s, dtype="fp32"):
+def conv1d_chunked(x, weight, bias, padding, dtype, chunk, residual=None, scale=1.0):
+    """A stride-1 conv1d_frames summed in blocks of `chunk` channels: output channels in blocks (concatenated), the
+    input channels of each in blocks whose partial convs are added in order (sum_div), then (y + residual) * scale.
+    The fp32 engine adds the C_in K products of an output in one chain (3,270 terms for the front-end's
+    1090-channel k3 convs), and its dx the C_out K products; blocks of 512 halve the rounding of both."""
+    Cout, Cin, _ = weight.shape
+    cols = []
+    for o0 in range(0, Cout, chunk):
+        wo = weight[o0:o0 + chunk]
+        bo = bias[o0:o0 + chunk] if bias is not None else None
+        parts = [conv1d_frames(x[..., c0:c0 + chunk], wo[:, c0:c0 + chunk], bo if c0 == 0 else None, 1, padding, 1,
+                               dtype) for c0 in range(0, Cin, chunk)]
+        cols.append(parts[0] if len(parts) == 1 else sum_div(parts))
+    y = cols[0] if len(cols) == 1 else torch.cat(cols, dim=-1)
+    return y if residual is None else sum_div([y, residual], 1.0 / scale)
+
+
+def adain_resblk1d_frames(m, x, s, dtype="fp32", kchunk=0):
     """AdainResBlk1d.forward (hifigan.py:384-403, dropout p = 0) on frames x [B, L, C_in] for any module with
     the reference's parameter layout (training.AdainResBlk1d or params.AdainResBlk1d):
     out = (conv2(LReLU(AdaIN2(conv1(pool(LReLU(AdaIN1(x))))))) + conv1x1(up2(x))) / sqrt(2), the sum and the
-    scale in conv2's epilogue."""
+    scale in conv2's epilogue.  kchunk > 0: the three convs through conv1d_chunked (fp32 accuracy)."""
     up = m.upsample if isinstance(getattr(m, "upsample", None), bool) else m.upsample_type != "none"
     # nn.Dropout(dropout_p) before each conv in train mode (models.py:335, 358-367; the predictor's blocks)
     # (the reference's AdainResBlk1d keeps only self.dropout = nn.Dropout(p), models.py:335: read its p then)
@@ -600,6 +622,13 @@ def adain_resblk1d_frames(m, x, s, dtype="fp32"):
     if up:
         r = _PoolFn.apply(r, _wn_w(m.pool), m.pool.bias)
     c1, c2 = m.conv1, m.conv2
+    if kchunk:
+        r = conv1d_chunked(dropout(r, p_drop), _wn_w(c1), c1.bias, 1, dtype, kchunk)
+        r = dropout(adain_act(r, s, m.norm2.fc.weight, m.norm2.fc.bias, None, ACT_LRELU), p_drop)
+        sc = _Up2Fn.apply(x) if up else x
+        if m.learned_sc:
+            sc = conv1d_chunked(sc, _wn_w(m.conv1x1), None, 0, dtype, kchunk)
+        return conv1d_chunked(r, _wn_w(c2), c2.bias, 1, dtype, kchunk, residual=sc, scale=1 / math.sqrt(2))
     r = conv1d_frames(dropout(r, p_drop), _wn_w(c1), c1.bias, 1, 1, dtype=dtype)
     r = dropout(adain_act(r, s, m.norm2.fc.weight, m.norm2.fc.bias, None, ACT_LRELU), p_drop)
     sc = _Up2Fn.apply(x) if up else x
@@ -1137,7 +1166,7 @@ def decoder_forward(dec, asr, F0_curve, N, s, noise=None, seed=None, utt_offset=
     return y.reshape(B, 1, -1)
 
 
-def _decoder_frontend(dec, asr, F0_curve, N, s, dtype):
+def _decoder_frontend(dec, asr, F0_curve, N, s, dtype, kchunk=0):
     """The front-end the three decoders share (hifigan.py:458-472 == vocos.py:404-418): the stride-2 F0 / N convs,
     encode, asr_res and the decode blocks with their concats -> frames [B, 2T, 512].  Reads either weight-norm
     layout (_wn_w)."""
@@ -1148,14 +1177,14 @@ def _decoder_frontend(dec, asr, F0_curve, N, s, dtype):
     Nc = conv1d_frames(N.unsqueeze(-1), _wn_w(dec.N_conv), dec.N_conv.bias, 2, 1, 1, dtype)
     asr_f = asr.transpose(1, 2)  # frames [B, T, 512]
     x = torch.cat([asr_f, F0, Nc], dim=2)
-    x = adain_resblk1d_frames(dec.encode, x, s, dtype)
+    x = adain_resblk1d_frames(dec.encode, x, s, dtype, kchunk)
     ar = dec.asr_res[0]
     asr_res = conv1d_frames(asr_f, _wn_w(ar), ar.bias, 1, 0, 1, dtype)
     res = True
     for block in dec.decode:
         if res:
             x = torch.cat([x, asr_res, F0, Nc], dim=2)
-        x = adain_resblk1d_frames(block, x, s, dtype)
+        x = adain_resblk1d_frames(block, x, s, dtype, kchunk)
         if block.upsample_type != "none":
             res = False
     return x
@@ -1342,6 +1371,158 @@ def vocos_decoder_forward(dec, asr, F0_curve, N, s, dtype="fp32"):
         F0_curve, N = train_smooth(F0_curve, N)
     x = _decoder_frontend(dec, asr, F0_curve, N, s, dtype)
     return vocos_generator_forward(dec.generator, x, s, dtype).unsqueeze(1)
+
+
+# ---------------------------------------------------------------------- iSTFTNet decoder (Modules/istftnet.py)
+FRONT_KCHUNK = 512  # channel block of the fp32 front-end convs of istft_decoder_forward (0 = one chain per output)
+class _CSTFTFn(torch.autograd.Function):
+    """CustomSTFT.transform (istftnet.py:207-243): wave [B, L] -> frames [B, L // hop + 1, n_fft + 2] (magnitude
+    channels, then phase).  The reference computes it under no_grad (:544-550): the output is a constant."""
+
+    @staticmethod
+    def forward(ctx, wave, wr, wi, n_fft, hop):
+        _require_device()
+        w = _f32(wave)
+        B, L = w.shape
+        nb = n_fft // 2 + 1
+        if wr.numel() != nb * n_fft or wi.numel() != nb * n_fft:
+            raise ValueError(f"CustomSTFT: forward bases {tuple(wr.shape)} / {tuple(wi.shape)} for n_fft {n_fft}")
+        out = torch.empty(B, L // hop + 1, n_fft + 2, dtype=torch.float32, device=w.device)
+        check(_tl().stts_cstft_fwd(_ptr(w), _ptr(_f32(wr)), _ptr(_f32(wi)), B, L, n_fft, hop, _ptr(out), _stream()),
+              "stts_cstft_fwd")
+        ctx.mark_non_differentiable(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        return None, None, None, None, None
+
+
+def cstft(wave, wr, wi, n_fft, hop):
+    return _CSTFTFn.apply(wave, wr, wi, int(n_fft), int(hop))
+
+
+class _PadLAddFn(torch.autograd.Function):
+    """reflection_pad((1, 0))(x) + src on frames (istftnet.py:558-561): x [B, L, C], src [B, L + 1, C]."""
+
+    @staticmethod
+    def forward(ctx, x, src):
+        _require_device()
+        B, L, C = x.shape
+        if tuple(src.shape) != (B, L + 1, C):
+            raise ValueError(f"padl_add: x {tuple(x.shape)}, src {tuple(src.shape)}: expected {(B, L + 1, C)}")
+        xc, sc = _f32(x), _f32(src)
+        y = torch.empty_like(sc)
+        check(_tl().stts_padl_add_fwd(_ptr(xc), _ptr(sc), B, L, C, _ptr(y), _stream()), "stts_padl_add_fwd")
+        ctx.shape = (B, L, C)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        B, L, C = ctx.shape
+        nx, ns = ctx.needs_input_grad
+        dx = None
+        if nx:
+            dy = _f32(gy)
+            dx = torch.empty(B, L, C, dtype=torch.float32, device=dy.device)
+            check(_tl().stts_padl_add_bwd(_ptr(dy), B, L, C, _ptr(dx), _stream()), "stts_padl_add_bwd")
+        return dx, (gy if ns else None)  # dx is its own tensor (see _SumDivFn.backward); src's gradient is dy itself
+
+
+def padl_add(x, src):
+    return _PadLAddFn.apply(x, src)
+
+
+class _CISTFTHeadFn(torch.autograd.Function):
+    """exp / sin -> CustomSTFT.inverse (istftnet.py:571-573, :246-293): post [B, F, n_fft + 2] -> audio
+    [B, (F - 1) hop].  Only `post` is saved; the bases are buffers (no gradient)."""
+
+    @staticmethod
+    def forward(ctx, post, br, bi, n_fft, hop):
+        _require_device()
+        B, F, W = post.shape
+        nb = n_fft // 2 + 1
+        if W != 2 * nb or br.numel() != nb * n_fft or bi.numel() != nb * n_fft:
+            raise ValueError(f"CustomSTFT head: post {tuple(post.shape)}, bases {tuple(br.shape)} / {tuple(bi.shape)} "
+                             f"for n_fft {n_fft}")
+        pc, brc, bic = _f32(post), _f32(br), _f32(bi)
+        y = torch.empty(B, max(F - 1, 0) * hop, dtype=torch.float32, device=pc.device)
+        check(_tl().stts_cistft_head_fwd(_ptr(pc), _ptr(brc), _ptr(bic), B, F, n_fft, hop, _ptr(y), _stream()),
+              "stts_cistft_head_fwd")
+        ctx.save_for_backward(pc, brc, bic)
+        ctx.geo = (n_fft, hop)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        pc, brc, bic = ctx.saved_tensors
+        n_fft, hop = ctx.geo
+        B, F, _ = pc.shape
+        dy = _f32(gy)
+        dp = torch.empty_like(pc)
+        check(_tl().stts_cistft_head_bwd(_ptr(pc), _ptr(brc), _ptr(bic), _ptr(dy), B, F, n_fft, hop, _ptr(dp),
+                                         _stream()), "stts_cistft_head_bwd")
+        return dp, None, None, None, None
+
+
+def cistft_head(post, br, bi, n_fft, hop):
+    return _CISTFTHeadFn.apply(post, br, bi, int(n_fft), int(hop))
+
+
+def istft_generator_forward(g, x, s, f0_curve, noise=None, seed=0, utt_offset=0, dtype="fp32"):
+    """Generator.forward (istftnet.py:543-573) on frames x [B, 2T, 512] for a module with the reference's parameter
+    layout (stts2_mi355x.istftnet.Generator) -> audio [B, 2T prod(rates) hop].  The harmonic source and its STFT
+    are constants, as under the reference's no_grad (:544-550): m_source.l_linear receives no gradient and
+    f0_curve's gradient comes through the front-end's F0_conv only."""
+    rates, kernels = g.upsample_rates, g.upsample_kernel_sizes
+    nk, last = g.num_kernels, len(rates) - 1
+    n_fft, hop = int(g.gen_istft_n_fft), int(g.gen_istft_hop_size)
+    st = g.stft
+    with torch.no_grad():
+        lin = g.m_source.l_linear
+        src = _SourceFn.apply(f0_curve.detach(), lin.weight.detach(), lin.bias.detach(), noise, seed, utt_offset,
+                              int(g.upsample_scale))  # [B, L], L = 2T prod(rates) hop
+        har = cstft(src, st.weight_forward_real, st.weight_forward_imag, n_fft, hop)  # frames [B, L / hop + 1, n_fft + 2]
+    for i, (u, k) in enumerate(zip(rates, kernels)):
+        nc = g.noise_convs[i]
+
+        def noise_branch(i=i, nc=nc):
+            x_src = conv1d_frames(har, nc.weight, nc.bias, int(nc.stride), int(nc.padding), 1, dtype)
+            return resblock1_frames(g.noise_res[i], x_src, s, dtype)
+
+        def up_branch(i=i, x=x):
+            x = leaky_relu(x, 0.1)
+            up = g.ups[i]
+            return conv_transpose1d_frames(x, _wn_w(up), up.bias, up.stride, up.padding, up.output_padding, dtype)
+
+        x, x_src = _branches([up_branch, noise_branch], (x, har, s))
+        x = padl_add(x, x_src) if i == last else sum_div([x, x_src])
+        rs = _branches([lambda j=j, x=x: resblock1_frames(g.resblocks[i * nk + j], x, s, dtype) for j in range(nk)],
+                       (x, s))
+        x = sum_div(rs, nk)
+    x = leaky_relu(x, 0.01)  # F.leaky_relu's default slope (:569)
+    cp = g.conv_post
+    post = conv1d_frames(x, _wn_w(cp), cp.bias, 1, cp.padding, 1, dtype)  # [B, F, n_fft + 2]
+    return cistft_head(post, st.weight_backward_real, st.weight_backward_imag, n_fft, hop)
+
+
+def istft_decoder_forward(dec, asr, F0_curve, N, s, noise=None, seed=None, utt_offset=0, dtype="fp32"):
+    """Decoder.forward (istftnet.py:692-721) with autograd through HIP kernels: asr [B, 512, T], F0_curve and
+    N [B, 2T], s [B, style_dim] -> [B, 1, 2T prod(rates) hop].  `dec` is stts2_mi355x.istftnet.Decoder; in .train()
+    mode the F0 / N smoothing of :693-701 is applied first (Python's random, as the reference).  `noise`
+    [B, L, 9] / `seed` / `utt_offset` as for hifigan.Decoder.  The convs take `dtype` (fp32, bf16, bf16x3); the
+    source, its STFT, the pad-add and the exp / sin -> inverse-STFT head are fp32 in all three."""
+    _require_device()
+    if dtype not in _DT:
+        raise ValueError(f"dtype {dtype!r}: expected one of {list(_DT)}")
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if noise is None else 0
+    if dec.training:
+        F0_curve, N = train_smooth(F0_curve, N)
+    # fp32 is the accuracy mode: its front-end convs are summed in 512-channel blocks (conv1d_chunked), since the
+    # AdaIN1d's of a short front-end (T = 4: four frames per statistic) amplify the convs' rounding ~30x in d asr
+    x = _decoder_frontend(dec, asr, F0_curve, N, s, dtype, kchunk=FRONT_KCHUNK if dtype == "fp32" else 0)
+    return istft_generator_forward(dec.generator, x, s, F0_curve, noise, seed, utt_offset, dtype).unsqueeze(1)
 
 
 # ---------------------------------------------------------------------- discriminators

@@ -43,7 +43,8 @@ static buffers and replay.  The returned losses are the graph's static outputs (
 the input gradients land on `static_inputs`; optimizer state["step"] follows after AdamW.sync_steps().
 The decoder may be a vocos.Decoder (its `noise=` / `seed=` keywords are accepted and ignored: Vocos has no source);
 that step runs eagerly only: `graph=True` raises NotImplementedError for it (the hipGraph capture of the Vocos step
-is not built).
+is not built).  It may also be an istftnet.Decoder (the harmonic source takes `noise=` / `seed=` as for HiFi-GAN;
+generator.m_source.l_linear gets no gradient, as in the reference, and AdamW skips it); eager only as well.
 `freeze_d_in_g` (default) turns off requires_grad of the discriminator parameters
 during the G step: the reference computes those gradients and discards them (its next iteration starts
 with zero_grad before they are used), so skipping them changes no update.
@@ -80,6 +81,9 @@ class TrainStep:
         self.graph = bool(graph)
         if self.graph and getattr(decoder, "decoder_type", None) == "vocos":
             raise NotImplementedError("TrainStep(graph=True) records the HiFi-GAN step; a Vocos decoder trains eagerly")
+        if self.graph and getattr(decoder, "decoder_type", None) == "istftnet":
+            raise NotImplementedError("TrainStep(graph=True) records the HiFi-GAN step; an iSTFTNet decoder trains "
+                                      "eagerly")
         self._graph, self._calls, self.static_inputs, self._static_out = None, 0, None, None
         mk = lambda m, lr: AdamW(m.parameters(), lr=lr, weight_decay=1e-4, betas=(0.0, 0.99), eps=1e-9,  # noqa: E731
                                  capturable=self.graph)
