@@ -41,6 +41,9 @@ typedef struct stts_model stts_model;
                                 cfg = {n, (fft_size, hop_size, win_length) x n}, the reference's
                                 {3, 1024, 120, 600, 2048, 240, 1200, 512, 50, 240} */
 #define STTS_KIND_VOCOS 5    /* Modules/vocos.py Decoder (front-end + ConvNeXt generator + ISTFTHead) */
+#define STTS_KIND_PITCH 8    /* Modules/JDC/model.py JDCNet (the frozen pitch extractor of the training step);
+                                cfg = {num_class}, the reference's {1}.  (7 stays an unknown kind: the ABI
+                                tests pin it as the rejected example.) */
 
 /* compute / activation dtypes */
 #define STTS_FP32 0 /* fp32 storage, exact-fp32 MFMA (parity mode)          */
@@ -83,7 +86,7 @@ long long stts_packed_bytes(const stts_model* m, int dtype);
 int stts_pack(stts_model* m, int dtype, void* packed, long long bytes, void* stream);
 
 /* Workspace for one forward of B utterances of T frames (decoder: T = asr frames;
- * F0N: T = text-aligned frames; STYLE: T = mel frames). */
+ * F0N: T = text-aligned frames; STYLE, PITCH: T = mel frames). */
 long long stts_workspace_bytes(const stts_model* m, int dtype, int B, int T);
 
 /* Decoder: asr [B][dim_in][T], F0_curve [B][2T], N [B][2T], s [B][style_dim] -> out [B][1][600T]
@@ -102,6 +105,22 @@ int stts_f0n_fwd(stts_model* m, int dtype, const float* x, const float* s, int B
 /* Style encoder: mel [B][1][80][T] -> style [B][style_dim]. */
 int stts_style_fwd(stts_model* m, int dtype, const float* mel, int B, int T, float* out, void* workspace,
                    long long ws_bytes, void* stream);
+
+/* Pitch extractor, <- Modules/JDC/model.py:102-137 JDCNet.forward in eval mode (train.py:261, under no_grad):
+ * mel [B][1][80][T] -> f0 [B][T][num_class] (after abs), and when the pointers are non-null gan_feature
+ * [B][256][10][T] (the LeakyReLU(BatchNorm(res_block3)) map, transposed as the reference returns it) and
+ * pool_out [B][256][T][2].  The BatchNorm layers use their running statistics (parameters of the plan); the
+ * detector branch, which forward never runs, is not part of the plan.  B >= 1, T >= 1.  The BiLSTM classifier
+ * runs the fp32 recurrence of stts_bilstm_fwd inside the plan's workspace: stts_pitch_error_offset is the byte
+ * offset of its error word in that workspace (read it as stts_bilstm_error_offset's), negative on bad
+ * arguments. */
+int stts_pitch_fwd(stts_model* m, int dtype, const float* mel, int B, int T, float* f0, float* gan_feature,
+                   float* pool_out, void* workspace, long long ws_bytes, void* stream);
+long long stts_pitch_error_offset(const stts_model* m, int dtype, int B, int T);
+
+/* utils.py:48-53 log_norm(x, mean, std, dim = the mel axis): mel [B][n_mels][T] -> out [B][T] =
+ * log(|| exp(x * std + mean) ||_2 over the n_mels bins), fp32 expf / logf, bins summed in a fixed order. */
+int stts_log_norm(const float* mel, int B, int n_mels, int T, float mean, float std, float* out, void* stream);
 
 /* MultiPeriodDiscriminator forward, <- Modules/discriminators.py:108-129 DiscriminatorP.forward for
  * every period (MultiPeriodDiscriminator.forward :143-156 calls it on y and y_hat: pass both as one

@@ -281,6 +281,30 @@ int st_istft_factor(int N, int* N1, int* N2);
 int st_scale_rows(const float* src, const float* scale, int rows_src, long long inner, int rows_dst, float* out,
                   hipStream_t s);
 
+// ---------------------------------------------------------------- pitch extractor (pitch.hip, JDCNet)
+// Its image is the reference's transposed mel: H = T frames, W = nb bins (padded frames as the style encoder's).
+// mel fp32 [B][1][nb][T] -> padded frames [T + 2][nb + 2] (channel 0), ld = 8
+int st_mel_to_padded_t(const float* mel, int B, int nb, int T, void* dst, int dtype, hipStream_t s);
+// eval-mode BatchNorm as a per-channel affine (pack time): ab[c] = w[c] / sqrt(var[c] + eps),
+// ab[C + c] = b[c] - mean[c] * ab[c]
+int st_bn_affine(const float* w, const float* b, const float* mean, const float* var, int C, float eps, float* ab,
+                 hipStream_t s);
+// BatchNorm affine -> LeakyReLU(slope) -> MaxPool over p adjacent columns (a tail shorter than p dropped): padded
+// x [H][W][C] -> padded y [H][W / p][C] with its zero borders (y may be null).  The last block's extras (each may be
+// null, fp32): seq [B][H][C (W / p)] (channel c (W / p) + w: the BiLSTM input), pool [B][C][H][W / p], and gan
+// [B][C][W][H], the activated map before the pooling.  C % 8 == 0.
+int st_bn_lrelu_maxpool(const void* x, int B, int H, int W, int C, const float* ab, float slope, int p, void* y,
+                        float* seq, float* gan, float* pool, int dtype, hipStream_t s);
+// out[r][n] = |bias[n] + sum_k w[n][k] x[r][k]| (k in order, fp32)
+int st_linear_abs(const float* x, long long rows, int K, const float* w, const float* bias, int N, float* out,
+                  hipStream_t s);
+int st_log_norm(const float* mel, int B, int n_mels, int T, float mean, float std, float* out, hipStream_t s);
+// stts_bilstm_fwd (prosody.hip) with the split-K input projection optional: without it the rows of an utterance do
+// not depend on the batch size
+int st_bilstm_fwd(const float* x, long long xs_b, long long xs_t, long long xs_c, int B, int T, int Cin,
+                  const int* lengths, const float* const* params, int H, float* y, float* h_n, float* c_n,
+                  void* workspace, long long ws_bytes, int splitk, hipStream_t s);
+
 // ---------------------------------------------------------------- training-step spectra (spec.hip)
 long long st_stft_frames(long long L, int hop);
 // torchaudio MelSpectrogram(sr, n_fft, win, hop, hann, n_mels) -> (log(1e-5 + mel) + 4) / 4:

@@ -1,4 +1,4 @@
-// Model plans (HiFi-GAN / iSTFTNet decoders, F0/N conv stacks, style encoder) and the
+// Model plans (HiFi-GAN / iSTFTNet decoders, F0/N conv stacks, style encoder, pitch extractor) and the
 // C-ABI declared in include/stts2.h.  A plan is built from the constructor arguments of the
 // reference module, names every parameter exactly like the reference state dict, packs the
 // weights (weight-norm fold + MFMA layout) into a caller buffer, and strings the gfx950
@@ -47,6 +47,12 @@ struct Params {
   const float* operator[](int i) const { return i < 0 ? nullptr : ptr[i]; }
 };
 
+// An eval-mode BatchNorm2d: its running statistics folded at pack time into (scale, shift) in the aux area
+struct BNorm {
+  int w = -1, b = -1, mean = -1, var = -1, C = 0;
+  size_t off = 0;  // aux: scale [C], then shift [C]
+};
+
 // A convolution whose weights are packed for conv1d_igemm.
 struct WConv {
   int v = -1, g = -1, bias = -1;
@@ -57,6 +63,9 @@ struct WConv {
   int rs = -1, src_rows = 0;
   size_t bias_aux = 0;
   bool aux_bias = false;
+  // pack-time prep (pitch extractor): the BatchNorm that follows the conv folded into it (rows scaled by its
+  // scale, its shift as the bias)
+  const BNorm* bn = nullptr;
   size_t off[ST_NDTYPES] = {0, 0, 0};
   // fold > 1: a stride-`fold` conv (padding fpad0) packed as the stride-1 conv over phase-folded frames
   // (fold consecutive input rows side by side): fold Cin channels, fK taps, padding fpad (k_fold_w)
@@ -183,6 +192,16 @@ struct stts_model {
     WConv convs[5], out;
   };
   std::vector<DiscS> msd;
+  // -------- pitch extractor (Modules/JDC/model.py JDCNet; forward :102-137)
+  struct PEBlk {
+    int cin = 0, cout = 0;
+    BNorm pre, mid;
+    WConv c1, c2, sc;
+  } pe_blk[3];
+  WConv pe_c0, pe_c1;
+  BNorm pe_bn0, pe_pool;
+  int pe_lstm[8] = {-1, -1, -1, -1, -1, -1, -1, -1}, pe_cls_w = -1, pe_cls_b = -1, pe_nclass = 0;
+  std::vector<BNorm*> bns;
   // -------- AdaIN projections (all AdaIN layers share one GEMV: H = s @ Wt + b)
   std::vector<WAdaIN*> adains;
   int Htot = 0;
@@ -445,6 +464,52 @@ int build_style(Model& m, const int* cfg, int n) {
   return ST_OK;
 }
 
+void add_bn(Model& m, BNorm& bn, const std::string& p, int C) {
+  bn.C = C;
+  bn.w = m.P.add(p + ".weight", C);
+  bn.b = m.P.add(p + ".bias", C);
+  bn.mean = m.P.add(p + ".running_mean", C);
+  bn.var = m.P.add(p + ".running_var", C);
+  m.bns.push_back(&bn);
+}
+
+// JDCNet(num_class) (Modules/JDC/model.py:14-72), the layers forward runs: conv_block, res_block1..3, pool_block,
+// bilstm_classifier, classifier.  The 3x3 weights [Cout][Cin][3][3] (frames x bins) are the 9-tap weights of the
+// (T x 80) image as they lie.  The detector branch is never run by forward and is not part of the plan.
+constexpr int kPitchCh[4] = {64, 128, 192, 256};
+constexpr int kPitchBins = 80, kPitchH = 256;
+constexpr float kPitchSlope = 0.01f;
+int build_pitch(Model& m, const int* cfg, int n) {
+  if (n != 1 || cfg[0] <= 0) return ST_EINVAL;
+  m.pe_nclass = cfg[0];
+  add_wconv(m, m.pe_c0, "conv_block.0", 1, 64, 9, false, false);
+  add_bn(m, m.pe_bn0, "conv_block.1", 64);
+  m.pe_c0.bn = &m.pe_bn0;
+  add_wconv(m, m.pe_c1, "conv_block.3", 64, 64, 9, false, false);
+  for (int i = 0; i < 3; ++i) {
+    auto& b = m.pe_blk[i];
+    const std::string p = "res_block" + std::to_string(i + 1);
+    b.cin = kPitchCh[i];
+    b.cout = kPitchCh[i + 1];
+    add_bn(m, b.pre, p + ".pre_conv.0", b.cin);
+    add_wconv(m, b.c1, p + ".conv.0", b.cin, b.cout, 9, false, false);
+    add_bn(m, b.mid, p + ".conv.1", b.cout);
+    b.c1.bn = &b.mid;
+    add_wconv(m, b.c2, p + ".conv.3", b.cout, b.cout, 9, false, false);
+    add_wconv(m, b.sc, p + ".conv1by1", b.cin, b.cout, 1, false, false);
+  }
+  add_bn(m, m.pe_pool, "pool_block.0", 256);
+  static const char* const ln[4] = {"weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0"};
+  for (int d = 0; d < 2; ++d)
+    for (int k = 0; k < 4; ++k) {
+      const long long numel = k == 0 ? 4LL * kPitchH * 512 : (k == 1 ? 4LL * kPitchH * kPitchH : 4LL * kPitchH);
+      m.pe_lstm[4 * d + k] = m.P.add(std::string("bilstm_classifier.") + ln[k] + (d ? "_reverse" : ""), numel);
+    }
+  m.pe_cls_w = m.P.add("classifier.weight", (long long)m.pe_nclass * 512);
+  m.pe_cls_b = m.P.add("classifier.bias", m.pe_nclass);
+  return ST_OK;
+}
+
 // MultiPeriodDiscriminator: DiscriminatorP(p) for each period (discriminators.py:132-141); each is
 // 5 weight-norm Conv2d (k, 1) stride (3, 1) [the last stride 1] + conv_post (3, 1)
 // (discriminators.py:96-106), i.e. 1-d convs along T/p with the same weight memory layout
@@ -571,10 +636,14 @@ void finalize_layout(Model& m) {
       c->bias_aux = a;
       a += rup((size_t)c->Cout * 4, ALIGN);
     }
+  for (auto* bn : m.bns) {
+    bn->off = a;
+    a += rup((size_t)2 * bn->C * 4, ALIGN);
+  }
   m.aux_bytes = a;
   size_t sc = 0;
   for (auto* c : m.convs) {
-    if (c->g >= 0 || c->reframe || c->rs >= 0 || c->src_rows) sc = std::max(sc, (size_t)c->Cin * c->Cout * c->K * 4);
+    if (c->g >= 0 || c->reframe || c->rs >= 0 || c->src_rows || c->bn) sc = std::max(sc, (size_t)c->Cin * c->Cout * c->K * 4);
     if (c->fold) sc = std::max(sc, rup((size_t)c->Cin * c->Cout * c->K * 4, ALIGN) + (size_t)c->pCin() * c->Cout * c->fK * 4);
   }
   m.scratch_bytes = rup(sc, ALIGN);
@@ -693,7 +762,7 @@ ConvParams conv_base(Ctx& c, const WConv& w, const Buf& x, int c0) {
   p.N = w.N();
   p.w = c.wpk(w);
   p.nchunks = (w.pCin() + 31) / 32;
-  p.bias = w.aux_bias ? c.aux_f(w.bias_aux) : c.P(w.bias);
+  p.bias = w.bn ? c.aux_f(w.bn->off) + w.bn->C : (w.aux_bias ? c.aux_f(w.bias_aux) : c.P(w.bias));
   p.Cout = w.Cout;
   p.pro = pro_none();
   p.up = 1;
@@ -1492,7 +1561,8 @@ Img img_alloc(Ctx& c, int H, int W, int C) {
   return im;
 }
 
-int conv3x3(Ctx& c, const WConv& w, const Img& x, const Img& y, int pro_lrelu, const Img* res) {
+int conv3x3(Ctx& c, const WConv& w, const Img& x, const Img& y, int pro_lrelu, const Img* res, float slope = 0.2f,
+            float res_scale = 0.70710678118654752440f) {
   ConvParams p = conv_base(c, w, x.b, 0);
   p.KS = 9;
   p.kw = 3;
@@ -1502,7 +1572,7 @@ int conv3x3(Ctx& c, const WConv& w, const Img& x, const Img& y, int pro_lrelu, c
   p.zc_valid = x.W;
   if (pro_lrelu) {
     p.pro.mode = PRO_LRELU;
-    p.pro.slope = 0.2f;
+    p.pro.slope = slope;
   }
   p.y = y.b.p ? y.b.p + (size_t)(x.W + 3) * y.C * c.esz : nullptr;
   p.y_bs = y.b.bs;
@@ -1512,7 +1582,7 @@ int conv3x3(Ctx& c, const WConv& w, const Img& x, const Img& y, int pro_lrelu, c
     p.res = res->b.p ? res->b.p + (size_t)(x.W + 3) * res->C * c.esz : nullptr;
     p.res_bs = res->b.bs;
     p.res_ld = res->C;
-    p.out_scale = (float)(1.0 / sqrt(2.0));
+    p.out_scale = res_scale;
   }
   return conv_run(c, p);
 }
@@ -1587,10 +1657,77 @@ int style_forward(Ctx& c, const float* mel, int T, float* out) {
   return 0;
 }
 
+// --------------------------------------------------------------------- pitch extractor forward
+// JDCNet.forward (Modules/JDC/model.py:102-137), eval mode.  The reference transposes the mel to (T frames x 80
+// bins) and pools the bins only, so the image is laid out H = T, W = bins: its Conv2d weights are conv3x3's taps as
+// they lie, MaxPool2d((1, p)) joins p adjacent rows of the flattened image, and every frame stays one image row up
+// to the [B][T][512] BiLSTM input.  err_off (may be null) receives the workspace offset of the BiLSTM error word.
+int pitch_forward(Ctx& c, const float* mel, int T, float* f0, float* gan, float* pool, size_t* err_off) {
+  Model& m = *c.m;
+  const int B = c.B, H = T;
+  Img M = img_alloc(c, H, kPitchBins, 8);
+  Img A = img_alloc(c, H, kPitchBins, 64);
+  Img X = img_alloc(c, H, kPitchBins, 64);
+  struct BI {
+    Img p, t, sc, y;
+  } bi[3];
+  int w = kPitchBins;
+  for (int i = 0; i < 3; ++i) {
+    const auto& k = m.pe_blk[i];
+    w /= 2;
+    bi[i].p = img_alloc(c, H, w, k.cin);
+    bi[i].t = img_alloc(c, H, w, k.cout);
+    bi[i].sc = img_alloc(c, H, w, k.cout);
+    bi[i].y = img_alloc(c, H, w, k.cout);
+  }
+  const size_t img_end = c.off;
+  const int F = kPitchCh[3] * (w / 4);  // 512 BiLSTM input features: channel c (w / 4) + bin
+  float* SEQ = reinterpret_cast<float*>(c.alloc((size_t)B * T * F * 4));
+  float* Y = reinterpret_cast<float*>(c.alloc((size_t)B * T * 2 * kPitchH * 4));
+  const long long lstm_bytes = stts_bilstm_workspace_bytes(B, T, kPitchH);
+  if (err_off) *err_off = c.off + (size_t)stts_bilstm_error_offset(B, T, kPitchH);
+  char* LW = c.alloc((size_t)lstm_bytes);
+  c.stats_begin = c.stats_off = c.off;
+  // zero borders of the images the convs write (and the unused channels of M)
+  if (!c.dry) ST_CHECK_HIP(hipMemsetAsync(c.ws, 0, img_end, c.s));
+  RUN(st_mel_to_padded_t(mel, B, kPitchBins, T, M.b.p, c.dtype, c.s));
+  RUN(conv3x3(c, m.pe_c0, M, A, 0, nullptr));                    // conv -> BN (folded)
+  RUN(conv3x3(c, m.pe_c1, A, X, 1, nullptr, kPitchSlope));       // LReLU -> conv
+  const Img* x = &X;
+  for (int i = 0; i < 3; ++i) {
+    const auto& k = m.pe_blk[i];
+    BI& t = bi[i];
+    RUN(st_bn_lrelu_maxpool(x->b.p, B, H, x->W, k.cin, c.aux_f(k.pre.off), kPitchSlope, 2, t.p.b.p, nullptr, nullptr,
+                            nullptr, c.dtype, c.s));            // pre_conv
+    {  // conv1by1 over every padded row of the pooled map (borders stay 0: no bias)
+      ConvParams p = conv_base(c, k.sc, t.p.b, 0);
+      p.Lq = (H + 2) * (t.p.W + 2);
+      conv_out(p, c, t.sc.b, 0, p.Lq);
+      RUN(conv_run(c, p));
+    }
+    RUN(conv3x3(c, k.c1, t.p, t.t, 0, nullptr));                            // conv -> BN (folded)
+    RUN(conv3x3(c, k.c2, t.t, t.y, 1, &t.sc, kPitchSlope, 1.0f));           // LReLU -> conv, + shortcut
+    x = &t.y;
+  }
+  RUN(st_bn_lrelu_maxpool(x->b.p, B, H, x->W, kPitchCh[3], c.aux_f(m.pe_pool.off), kPitchSlope, 4, nullptr, SEQ, gan,
+                          pool, c.dtype, c.s));                  // pool_block
+  if (!c.dry) {
+    const float* lp[8];
+    for (int k = 0; k < 8; ++k) lp[k] = c.P(m.pe_lstm[k]);
+    ST_CHECK(st_bilstm_fwd(SEQ, (long long)T * F, F, 1, B, T, F, nullptr, lp, kPitchH, Y, nullptr, nullptr, LW,
+                           lstm_bytes, 0, c.s));
+  }
+  RUN(st_linear_abs(Y, (long long)B * T, 2 * kPitchH, c.P(m.pe_cls_w), c.P(m.pe_cls_b), m.pe_nclass, f0, c.s));
+  return 0;
+}
+
 // --------------------------------------------------------------------- packing
 int pack_model(Model& m, int dt, char* base, hipStream_t s) {
   char* aux = base + m.aux_off[dt];
   float* scratch = reinterpret_cast<float*>(base + m.scratch_off[dt]);
+  for (auto* bn : m.bns)
+    ST_CHECK(st_bn_affine(m.P[bn->w], m.P[bn->b], m.P[bn->mean], m.P[bn->var], bn->C, 1e-5f,
+                          reinterpret_cast<float*>(aux + bn->off), s));
   for (auto* c : m.convs) {
     const float* v = m.P[c->v];
     const float* src = v;
@@ -1601,6 +1738,10 @@ int pack_model(Model& m, int dt, char* base, hipStream_t s) {
       src = scratch;
     } else if (c->reframe) {
       ST_CHECK(st_reframe_w(v, c->Cout, c->reframe, scratch, s));
+      src = scratch;
+    } else if (c->bn) {
+      ST_CHECK(st_scale_rows(v, reinterpret_cast<const float*>(aux + c->bn->off), c->Cout, (long long)c->Cin * c->K,
+                             c->Cout, scratch, s));
       src = scratch;
     } else if (c->rs >= 0 || c->src_rows) {
       const int rows = c->src_rows ? c->src_rows : c->Cout;
@@ -1691,6 +1832,8 @@ int stts_model_create(int kind, const int* cfg, int ncfg, stts_model** out) {
     r = build_vocos(*m, cfg, ncfg);
   else if (kind == STTS_KIND_MSD)
     r = build_msd(*m, cfg, ncfg);
+  else if (kind == STTS_KIND_PITCH)
+    r = build_pitch(*m, cfg, ncfg);
   if (r != 0) {
     delete m;
     return r;
@@ -1759,6 +1902,9 @@ long long stts_workspace_bytes(const stts_model* mc, int dtype, int B, int T) {
     DecIO io{};
     io.T = T;
     r = with_ctx(m, dtype, B, nullptr, 0, nullptr, [&](Ctx& c) { return vocos_forward(c, io); }, &need);
+  } else if (m->kind == STTS_KIND_PITCH) {
+    r = with_ctx(m, dtype, B, nullptr, 0, nullptr,
+                 [&](Ctx& c) { return pitch_forward(c, nullptr, T, nullptr, nullptr, nullptr, nullptr); }, &need);
   } else {
     r = with_ctx(m, dtype, B, nullptr, 0, nullptr, [&](Ctx& c) { return style_forward(c, nullptr, T, nullptr); },
                  &need);
@@ -1794,6 +1940,27 @@ int stts_style_fwd(stts_model* m, int dtype, const float* mel, int B, int T, flo
   if (B <= 0 || T <= 0 || !mel || !out) return ST_EINVAL;
   ST_CHECK(check_params(*m));
   return with_ctx(m, dtype, B, ws, ws_bytes, stream, [&](Ctx& c) { return style_forward(c, mel, T, out); }, nullptr);
+}
+
+int stts_pitch_fwd(stts_model* m, int dtype, const float* mel, int B, int T, float* f0, float* gan_feature,
+                   float* pool_out, void* ws, long long ws_bytes, void* stream) {
+  if (!m || m->kind != STTS_KIND_PITCH) return ST_EINVAL;
+  if (B <= 0 || T <= 0 || !mel || !f0) return ST_EINVAL;
+  ST_CHECK(check_params(*m));
+  return with_ctx(m, dtype, B, ws, ws_bytes, stream,
+                  [&](Ctx& c) { return pitch_forward(c, mel, T, f0, gan_feature, pool_out, nullptr); }, nullptr);
+}
+
+long long stts_pitch_error_offset(const stts_model* mc, int dtype, int B, int T) {
+  if (!mc || mc->kind != STTS_KIND_PITCH || B <= 0 || T <= 0) return ST_EINVAL;
+  size_t need = 0, off = 0;
+  const int r = with_ctx(const_cast<Model*>(mc), dtype, B, nullptr, 0, nullptr,
+                         [&](Ctx& c) { return pitch_forward(c, nullptr, T, nullptr, nullptr, nullptr, &off); }, &need);
+  return r ? r : (long long)off;
+}
+
+int stts_log_norm(const float* mel, int B, int n_mels, int T, float mean, float std, float* out, void* stream) {
+  return st_log_norm(mel, B, n_mels, T, mean, std, out, (hipStream_t)stream);
 }
 
 long long stts_mpd_out_elems(const stts_model* m, int B, int T) {

@@ -16,6 +16,7 @@
 // batch_first LSTMs use.  Everything here is latency-bound at text lengths (T <= a few
 // hundred tokens): the kernels aim at few launches and no host round trips, not at MFMA.
 #include "common.h"
+#include "kernels.h"
 #include "stts2.h"
 
 // ---------------------------------------------------------------------------------------
@@ -682,16 +683,19 @@ long long stts_bilstm_error_offset(int B, int T, int H) {
   return lstm_err_off(B, T, H);
 }
 
-int stts_bilstm_fwd(const float* x, long long xs_b, long long xs_t, long long xs_c, int B, int T, int Cin,
-                    const int* lengths, const float* const* params, int H, float* y, float* h_n, float* c_n,
-                    void* workspace, long long ws_bytes, void* stream) {
+}  // extern "C"
+
+// splitk == 0: the input projections never take the split-K path (its split count depends on B T), so an
+// utterance's outputs do not depend on the batch it came in (the pitch extractor's plan, plan.cpp)
+int st_bilstm_fwd(const float* x, long long xs_b, long long xs_t, long long xs_c, int B, int T, int Cin,
+                  const int* lengths, const float* const* params, int H, float* y, float* h_n, float* c_n,
+                  void* workspace, long long ws_bytes, int splitk, hipStream_t s) {
   if (B < 0 || T < 0 || Cin <= 0 || !params || !y) return ST_EINVAL;
   if (H <= 0 || H > 256 || (H & 31)) return ST_EINVAL;  // 4H lanes per workgroup, chunks of 8 k-quads
   for (int i = 0; i < 8; ++i)
     if (!params[i]) return ST_EPARAMS;
   if (ws_bytes < stts_bilstm_workspace_bytes(B, T, H)) return ST_EWORKSPACE;
   if (B == 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
   int* err = (int*)((char*)workspace + lstm_err_off(B, T, H));
   ST_CHECK_HIP(hipMemsetAsync(err, 0, sizeof(int), s));  // the host reads it (stts_bilstm_error_offset)
   float* G = (float*)workspace;
@@ -707,7 +711,7 @@ int stts_bilstm_fwd(const float* x, long long xs_b, long long xs_t, long long xs
       const float* const* p = params + 4 * d;
       GemmArgs a{x, xs_b, xs_t, xs_c, T, Cin, p[0], 0, Cin, 1, 0, H4, 1, 0, p[2], p[3],
                  G + (size_t)d * B * T * H4, (long long)T * H4, H4, 1, T, 1, 0, nullptr};
-      const long long pe = lstm_part_elems(B, T, H);
+      const long long pe = splitk ? lstm_part_elems(B, T, H) : 0;
       float* part = pe ? (float*)((char*)workspace + (stts_bilstm_workspace_bytes(B, T, H) - pe * (long long)sizeof(float)))
                        : nullptr;
       ST_CHECK(launch_gemm(a, B, s, part, pe));
@@ -749,6 +753,15 @@ int stts_bilstm_fwd(const float* x, long long xs_b, long long xs_t, long long xs
   else
     hipLaunchKernelGGL(k_bilstm_rec<1>, dim3(B, 2), dim3(H4), 0, s, G, reinterpret_cast<const float4*>(WT), lengths, B, T, H, y, h_n, c_n, nullptr);
   return (int)hipGetLastError();
+}
+
+extern "C" {
+
+int stts_bilstm_fwd(const float* x, long long xs_b, long long xs_t, long long xs_c, int B, int T, int Cin,
+                    const int* lengths, const float* const* params, int H, float* y, float* h_n, float* c_n,
+                    void* workspace, long long ws_bytes, void* stream) {
+  return st_bilstm_fwd(x, xs_b, xs_t, xs_c, B, T, Cin, lengths, params, H, y, h_n, c_n, workspace, ws_bytes, 1,
+                       (hipStream_t)stream);
 }
 
 int stts_row_norm(const float* x, long long xs_b, long long xs_t, long long xs_c, int B, int T, int C, int mode,

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 KIND_HIFIGAN, KIND_ISTFTNET, KIND_F0N, KIND_STYLE, KIND_MPD, KIND_VOCOS, KIND_MSD = 0, 1, 2, 3, 4, 5, 6
+KIND_PITCH = 8  # (7 is not a kind: include/stts2.h)
 DTYPES = {"fp32": 0, "bf16": 1, "bf16x3": 2}  # bf16x3: the split-operand accuracy mode (STTS_SPLIT)
 
 _LIB = None
@@ -65,6 +66,12 @@ def lib():
     L.stts_f0n_fwd.restype = c_int
     L.stts_style_fwd.argtypes = [c_vp, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_ll, c_vp]
     L.stts_style_fwd.restype = c_int
+    L.stts_pitch_fwd.argtypes = [c_vp, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_ll, c_vp]
+    L.stts_pitch_fwd.restype = c_int
+    L.stts_pitch_error_offset.argtypes = [c_vp, c_int, c_int, c_int]
+    L.stts_pitch_error_offset.restype = c_ll
+    L.stts_log_norm.argtypes = [c_vp, c_int, c_int, c_int, ctypes.c_float, ctypes.c_float, c_vp, c_vp]
+    L.stts_log_norm.restype = c_int
     L.stts_mpd_out_elems.argtypes = [c_vp, c_int, c_int]
     L.stts_mpd_out_elems.restype = c_ll
     L.stts_mpd_fwd.argtypes = [c_vp, c_int, c_vp, c_int, c_int, c_vp, c_ll, c_vp, c_ll, c_vp]
@@ -479,6 +486,61 @@ class StyleEngine(_Engine):
         check(lib().stts_style_fwd(self.model.h, DTYPES[self.dtype], _ptr(mel), B, T, _ptr(out), _ptr(ws), nb,
                                    _stream()), "stts_style_fwd")
         return out if in_dev.type == "cuda" else out.to(in_dev)
+
+
+class PitchEngine(_Engine):
+    """HIP forward of Modules/JDC/model.py JDCNet (reference :102-137, eval mode).  The plan binds the BatchNorm
+    running statistics like any other parameter, so the packed folds go stale (stale()) when one changes."""
+
+    def __init__(self, module, dtype="fp32"):
+        super().__init__(module, dtype)
+        self.num_class = module.num_class
+        self.model = NativeModel(KIND_PITCH, [module.num_class], module)
+        self.model.pack(dtype)
+
+    def forward(self, mel, features=True):
+        """mel [B, 1, 80, T] -> (f0 [B, T, num_class], GAN_feature [B, 256, 10, T], poolblock_out [B, 256, T, 2]);
+        features=False passes null pointers for the two feature maps (they come back as None)."""
+        from . import prosody
+        dev = self.model.device
+        in_dev = mel.device
+        mel = _dev_f32(mel, dev)
+        if mel.dim() != 4 or mel.shape[1] != 1 or mel.shape[2] != 80 or mel.shape[0] < 1 or mel.shape[3] < 1:
+            raise ValueError(f"mel must be [B, 1, 80, T], got {tuple(mel.shape)}")
+        B, _, _, T = mel.shape
+        f0 = torch.empty(B, T, self.num_class, dtype=torch.float32, device=dev)
+        gan = torch.empty(B, 256, 10, T, dtype=torch.float32, device=dev) if features else None
+        pool = torch.empty(B, 256, T, 2, dtype=torch.float32, device=dev) if features else None
+        ws, nb = self.model.workspace(self.dtype, B, T)
+        L = lib()
+        check(L.stts_pitch_fwd(self.model.h, DTYPES[self.dtype], _ptr(mel), B, T, _ptr(f0), _ptr(gan), _ptr(pool),
+                               _ptr(ws), nb, _stream()), "stts_pitch_fwd")
+        # the cooperative BiLSTM recurrence's time-out word, checked with the other BiLSTM launches' words
+        off = int(L.stts_pitch_error_offset(self.model.h, DTYPES[self.dtype], B, T))
+        check(off if off < 0 else 0, "stts_pitch_error_offset")
+        if len(prosody._PENDING) >= 64:
+            prosody.check_pending()
+        prosody._PENDING.append((f"JDCNet bilstm_classifier B={B} T={T}", ws[off:off + 4].view(torch.int32).clone()))
+        if in_dev.type != "cuda":
+            f0, gan, pool = (t.to(in_dev) if t is not None else None for t in (f0, gan, pool))
+        return f0, gan, pool
+
+
+def log_norm(x, mean=-4, std=4, dim=2):
+    """utils.py:48-53 on the HIP path (stts_log_norm), for the call train.py:262 makes: x [B, 1, n_mels, T] with
+    dim = 2 (the mel axis) -> [B, 1, T] = log(|| exp(x * std + mean) ||_2)."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[1] != 1 or dim != 2:
+        raise NotImplementedError("log_norm: the HIP path serves train.py:262's call only, x [B, 1, n_mels, T] with "
+                                  f"dim=2 (got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)}, dim={dim})")
+    _require_device()
+    dev = x.device if x.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    in_dev = x.device
+    m = _dev_f32(x, dev)
+    B, _, M, T = m.shape
+    out = torch.empty(B, 1, T, dtype=torch.float32, device=dev)
+    if B and T:
+        check(lib().stts_log_norm(_ptr(m), B, M, T, float(mean), float(std), _ptr(out), _stream()), "stts_log_norm")
+    return out if in_dev.type == "cuda" else out.to(in_dev)
 
 
 MPD_CH = (1, 32, 128, 512, 1024, 1024, 1)

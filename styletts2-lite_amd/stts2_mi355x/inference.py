@@ -232,10 +232,12 @@ def symbol_table(config):
     return table, len(table) + 1
 
 
-def build_models(config):
+def build_models(config, pitch_extractor=False):
     """inference.py:88-122 with the drop-in classes: the parsed config.yaml (a dict) ->
     {'decoder', 'predictor', 'text_encoder', 'style_encoder'} modules (parameters on the CPU,
-    move them with .to('cuda'))."""
+    move them with .to('cuda')).  pitch_extractor=True adds the training step's frozen
+    'pitch_extractor' (jdc.JDCNet from config['model_params']['JDC_params'], models.py build_model), which
+    load_models then fills from the checkpoint's entry of that name."""
     from . import hifigan, istftnet, vocos
     from .models import ProsodyPredictor, StyleEncoder, TextEncoder
     args = config["model_params"]
@@ -257,7 +259,7 @@ def build_models(config):
                                    gen_istft_hop_size=dec["gen_istft_hop_size"])
     elif dec["type"] == "hifigan":
         decoder = hifigan.Decoder(**common)
-    return {
+    models = {
         "decoder": decoder,
         "predictor": ProsodyPredictor(style_dim=args["style_dim"], d_hid=args["hidden_dim"], nlayers=args["n_layer"],
                                       max_dur=args["max_dur"], dropout=args["dropout"]),
@@ -266,6 +268,11 @@ def build_models(config):
         "style_encoder": StyleEncoder(dim_in=args["dim_in"], style_dim=args["style_dim"],
                                       max_conv_dim=args["hidden_dim"]),
     }
+    if pitch_extractor:
+        from .jdc import JDCNet
+        jdc = args["JDC_params"]
+        models["pitch_extractor"] = JDCNet(num_class=jdc["num_class"], seq_len=jdc["seq_len"])
+    return models
 
 
 def load_models(model, models_path):

@@ -9,6 +9,8 @@
   one `stts_gan_loss` launch sequence over all the terms of a call (fixed-order fp64 sums), gradients
   by `stts_gan_loss_bwd`.  They take the reference's lists of tensors (scores [B, n], feature maps of any
   layout as long as the real and generated maps of one layer share it).
+* `log_norm(x, mean=-4, std=4, dim=2)` (utils.py:48-53): the norm-consistency target of train.py:262, by
+  `stts_log_norm` (no gradient: the reference calls it under no_grad).
 """
 from __future__ import annotations
 
@@ -18,6 +20,7 @@ import torch
 from torch import nn
 
 from .engine import _ptr, _require_device, _stream, check
+from .engine import log_norm  # noqa: F401  (utils.py:48-53, the N_real target of train.py:262)
 from .training import _f32, _tl, _ws
 
 GAN_FEATURE, GAN_GEN, GAN_DISC, GAN_TPRLS = 0, 1, 2, 3

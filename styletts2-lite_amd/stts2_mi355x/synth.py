@@ -125,11 +125,20 @@ def synth_param(key: str, shape) -> np.ndarray:
         return uniform(key, shape, 0.8, 1.2)
     if key.endswith(".beta"):
         return uniform(key, shape, -0.1, 0.1)
+    # BatchNorm (the pitch extractor): after every rule above, so no earlier key changes value
+    if key.endswith(".weight") and len(shape) == 1:
+        return uniform(key, shape, 0.8, 1.2)
+    if key.endswith("running_mean"):
+        return uniform(key, shape, -0.1, 0.1)
+    if key.endswith("running_var"):  # positive
+        return uniform(key, shape, 0.5, 1.5)
     raise KeyError(f"no synthesis rule for {key} {shape}")
 
 
 def is_fixed_buffer(key: str) -> bool:
     """Deterministic buffers the modules compute themselves (CustomSTFT bases)."""
+    if key.endswith("num_batches_tracked"):  # BatchNorm's step counter: the module's own value stays
+        return True
     return ".stft." in key and not key.endswith((".out.weight", ".out.bias"))  # Vocos ISTFTHead.out is a Linear
 
 

@@ -19,9 +19,11 @@ require grad.  With `predictor=` and `style_encoder=` the G step also runs them 
 
 computes s = style_encoder(gt.unsqueeze(1)), (F0_fake, N_fake) = predictor.F0Ntrain(p_en, s) (the predictor in
 train mode: its dropout), y_rec = decoder(en, F0_fake, N_fake, s), adds lambda_F0 smooth_l1(F0_real, F0_fake) / 10
-and lambda_norm smooth_l1(N_real, N_fake) to g_loss (:269-270, 300-307; F0_real comes from the pitch extractor and
-N_real = log_norm(gt), both outside this path) and steps AdamW on the predictor and the style encoder after the
-decoder's backward (:323-324).  With `text_encoder=` (and the predictor) the step starts where train.py's G step starts
+and lambda_norm smooth_l1(N_real, N_fake) to g_loss (:269-270, 300-307) and steps AdamW on the predictor and the
+style encoder after the decoder's backward (:323-324).  F0_real and N_real are the caller's tensors, or, with
+`pitch_extractor=` (a jdc.JDCNet in eval mode) and none given, what train.py:260-262 computes from gt under no_grad:
+F0_real = pitch_extractor(gt.unsqueeze(1))[0] and N_real = log_norm(gt.unsqueeze(1)).squeeze(1), both on the HIP path
+(`TrainStep.targets(gt)`); the extractor is frozen: no optimizer, no gradient.  With `text_encoder=` (and the predictor) the step starts where train.py's G step starts
 (train.py:217-262), from the tokens:
 
     losses = step(None, None, None, None, wav, gt=None, F0_real=F0_real, N_real=N_real,
@@ -68,8 +70,9 @@ class TrainStep:
     def __init__(self, decoder, mpd, msd, lr_dec=1e-5, lr_disc=1e-4, lambda_mel=5.0, lambda_gen=1.0, dtype="fp32",
                  freeze_d_in_g=True, capture=False, predictor=None, style_encoder=None, lr_pred=1e-4, lr_style=1e-5,
                  lambda_F0=1.0, lambda_norm=1.0, text_encoder=None, lr_text=1e-4, lambda_dur=1.0, lambda_ce=1.0,
-                 graph=False):
+                 graph=False, pitch_extractor=None):
         self.decoder, self.mpd, self.msd = decoder, mpd, msd
+        self.pitch_extractor = pitch_extractor  # frozen (train.py:260-261): no optimizer, no gradient
         self.predictor, self.style_encoder, self.text_encoder = predictor, style_encoder, text_encoder
         self.lambda_dur, self.lambda_ce = float(lambda_dur), float(lambda_ce)
         self.lambda_F0, self.lambda_norm = float(lambda_F0), float(lambda_norm)
@@ -176,6 +179,16 @@ class TrainStep:
                     raise ValueError("TrainStep(graph=True): the graph was recorded with explicit noise, pass noise=")
                 st["seed"].fill_(seed_i64(seed))
 
+    def targets(self, gt):
+        """train.py:260-262: (F0_real, N_real) of the cropped mel gt [B, 80, T], under no_grad."""
+        from .losses import log_norm
+        if self.pitch_extractor is None:
+            raise ValueError("TrainStep.targets needs pitch_extractor=")
+        with torch.no_grad():
+            F0_real, _, _ = self.pitch_extractor(gt.unsqueeze(1))
+            N_real = log_norm(gt.unsqueeze(1)).squeeze(1)
+        return F0_real, N_real
+
     def _text_front(self, text):
         """train.py:217-251: the text encoder, asr, the predictor's forward and the crops."""
         from .prosody import matmul
@@ -204,6 +217,8 @@ class TrainStep:
             text_losses = (loss_dur, loss_ce)
         if self.style_encoder is not None and gt is not None:
             s = self.style_encoder(gt.unsqueeze(1))  # train.py:258
+        if self.pitch_extractor is not None and gt is not None and F0_real is None and N_real is None:
+            F0_real, N_real = self.targets(gt)  # train.py:260-262 (explicit targets win)
         if self.predictor is not None and p_en is not None:
             F0, N = self.predictor.F0Ntrain(p_en, s)  # train.py:265
         y_rec = self.decoder(en, F0, N, s, noise=noise, seed=seed, dtype=self.dtype)
