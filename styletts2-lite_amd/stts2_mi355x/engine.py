@@ -14,6 +14,8 @@ import os
 import numpy as np
 import torch
 
+from .abi import SIGNATURES
+
 KIND_HIFIGAN, KIND_ISTFTNET, KIND_F0N, KIND_STYLE, KIND_MPD, KIND_VOCOS, KIND_MSD = 0, 1, 2, 3, 4, 5, 6
 KIND_PITCH = 8  # (7 is not a kind: include/stts2.h)
 DTYPES = {"fp32": 0, "bf16": 1, "bf16x3": 2}  # bf16x3: the split-operand accuracy mode (STTS_SPLIT)
@@ -22,13 +24,14 @@ _LIB = None
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (STTS_LIB: another build of the same C-ABI revision, for build-against-build A/Bs on one box: tools/gpu/)
 LIB_PATH = os.environ.get("STTS_LIB") or os.path.join(_HERE, "libstts2.so")
-ABI_VERSION = 5  # include/stts2.h STTS_ABI_VERSION: the signatures bound below
+ABI_VERSION = 5  # include/stts2.h STTS_ABI_VERSION: the revision abi.SIGNATURES describes
 
-c_int, c_ll, c_ull, c_vp, c_fp = ctypes.c_int, ctypes.c_longlong, ctypes.c_ulonglong, ctypes.c_void_p, ctypes.c_void_p
+c_int, c_ll, c_vp = ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p
 
 
 def lib():
-    """Load libstts2.so (after torch, so both share torch's HIP runtime)."""
+    """Load libstts2.so (after torch, so both share torch's HIP runtime) and give every entry point its signature
+    (abi.SIGNATURES): the one place the library is bound, whichever module calls it."""
     global _LIB
     if _LIB is not None:
         return _LIB
@@ -36,138 +39,16 @@ def lib():
         raise RuntimeError(f"{LIB_PATH} missing: build it with `python -m stts2_mi355x.build` "
                            "(__graft_entry__.build()); there is no non-HIP fallback")
     L = ctypes.CDLL(LIB_PATH)
-    L.stts_abi_version.argtypes = []
-    L.stts_abi_version.restype = c_int
-    if L.stts_abi_version() != ABI_VERSION:
-        raise RuntimeError(f"{LIB_PATH}: C-ABI revision {L.stts_abi_version()}, these bindings expect {ABI_VERSION} "
+    # (an int return and no arguments are ctypes' defaults, so the revision is read before the table is applied)
+    rev = L.stts_abi_version() if hasattr(L, "stts_abi_version") else None
+    if rev != ABI_VERSION:
+        raise RuntimeError(f"{LIB_PATH}: C-ABI revision {rev}, these bindings expect {ABI_VERSION} "
                            "(include/stts2.h STTS_ABI_VERSION): rebuild the library")
-    L.stts_model_create.argtypes = [c_int, ctypes.POINTER(c_int), c_int, ctypes.POINTER(c_vp)]
-    L.stts_model_create.restype = c_int
-    L.stts_model_destroy.argtypes = [c_vp]
-    L.stts_model_destroy.restype = None
-    L.stts_param_count.argtypes = [c_vp]
-    L.stts_param_count.restype = c_int
-    L.stts_param_name.argtypes = [c_vp, c_int]
-    L.stts_param_name.restype = ctypes.c_char_p
-    L.stts_param_numel.argtypes = [c_vp, c_int]
-    L.stts_param_numel.restype = c_ll
-    L.stts_set_param.argtypes = [c_vp, c_int, c_vp]
-    L.stts_set_param.restype = c_int
-    L.stts_packed_bytes.argtypes = [c_vp, c_int]
-    L.stts_packed_bytes.restype = c_ll
-    L.stts_pack.argtypes = [c_vp, c_int, c_vp, c_ll, c_vp]
-    L.stts_pack.restype = c_int
-    L.stts_workspace_bytes.argtypes = [c_vp, c_int, c_int, c_int]
-    L.stts_workspace_bytes.restype = c_ll
-    L.stts_decoder_fwd.argtypes = [c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_ull, c_ll, c_int, c_int, c_vp, c_vp,
-                                   c_ll, c_vp]
-    L.stts_decoder_fwd.restype = c_int
-    L.stts_f0n_fwd.argtypes = [c_vp, c_int, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_ll, c_vp]
-    L.stts_f0n_fwd.restype = c_int
-    L.stts_style_fwd.argtypes = [c_vp, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_ll, c_vp]
-    L.stts_style_fwd.restype = c_int
-    L.stts_pitch_fwd.argtypes = [c_vp, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_ll, c_vp]
-    L.stts_pitch_fwd.restype = c_int
-    L.stts_pitch_error_offset.argtypes = [c_vp, c_int, c_int, c_int]
-    L.stts_pitch_error_offset.restype = c_ll
-    L.stts_log_norm.argtypes = [c_vp, c_int, c_int, c_int, ctypes.c_float, ctypes.c_float, c_vp, c_vp]
-    L.stts_log_norm.restype = c_int
-    L.stts_mpd_out_elems.argtypes = [c_vp, c_int, c_int]
-    L.stts_mpd_out_elems.restype = c_ll
-    L.stts_mpd_fwd.argtypes = [c_vp, c_int, c_vp, c_int, c_int, c_vp, c_ll, c_vp, c_ll, c_vp]
-    L.stts_mpd_fwd.restype = c_int
-    L.stts_mpd_losses.argtypes = [c_vp, c_int, c_int, c_vp, c_vp, c_ll, c_vp, c_vp]
-    L.stts_mpd_losses.restype = c_int
-    L.stts_msd_out_elems.argtypes = [c_vp, c_int, c_int]
-    L.stts_msd_out_elems.restype = c_ll
-    L.stts_msd_fwd.argtypes = [c_vp, c_int, c_vp, c_int, c_int, c_vp, c_ll, c_vp, c_ll, c_vp]
-    L.stts_msd_fwd.restype = c_int
-    L.stts_msd_losses.argtypes = [c_vp, c_int, c_int, c_vp, c_vp, c_ll, c_vp, c_vp]
-    L.stts_gan_losses_scratch_bytes.argtypes = [c_vp]
-    L.stts_gan_losses_scratch_bytes.restype = c_ll
-    L.stts_msd_losses.restype = c_int
-    for fn in ("stts_conv1d_fwd_workspace_bytes", "stts_conv1d_bwd_workspace_bytes",
-               "stts_conv1d_fwd_tx_workspace_bytes", "stts_conv1d_bwd_tx_workspace_bytes"):
-        getattr(L, fn).argtypes = [c_int] * 10
-        getattr(L, fn).restype = c_ll
-    L.stts_conv1d_fwd.argtypes = [c_int, c_vp, c_vp, c_vp] + [c_int] * 9 + [c_vp, c_vp, c_ll, c_vp]
-    L.stts_conv1d_fwd.restype = c_int
-    L.stts_conv1d_fwd_act.argtypes = [c_int, c_vp, c_vp, c_vp] + [c_int] * 9 + [ctypes.c_float, c_vp, c_vp, c_ll,
-                                                                                  c_vp]
-    L.stts_conv1d_fwd_act.restype = c_int
-    L.stts_conv1d_fwd_tx.argtypes = [c_int, c_vp, c_vp, c_vp] + [c_int] * 10 + [ctypes.c_float, c_vp, c_vp, c_ll, c_vp]
-    L.stts_conv1d_fwd_tx.restype = c_int
-    L.stts_conv1d_bwd_tx.argtypes = [c_int, c_vp, c_vp] + [c_int] * 9 + [c_vp, c_vp, c_ll, c_vp]
-    L.stts_conv1d_bwd_tx.restype = c_int
-    L.stts_conv1d_wgrad_tx.argtypes = [c_int, c_vp, c_vp] + [c_int] * 9 + [c_vp, c_vp, c_vp, c_ll, c_vp]
-    L.stts_conv1d_wgrad_tx.restype = c_int
-    L.stts_conv1d_fwd_res.argtypes = [c_int, c_vp, c_vp, c_vp, c_vp, ctypes.c_float] + [c_int] * 9 + [c_vp, c_vp,
-                                                                                                   c_ll, c_vp]
-    L.stts_pool_workspace_bytes.argtypes = [c_int, c_int, c_int]
-    L.stts_pool_workspace_bytes.restype = c_ll
-    L.stts_pool_fwd.argtypes = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]
-    L.stts_pool_fwd.restype = c_int
-    L.stts_pool_bwd.argtypes = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_ll, c_vp]
-    L.stts_pool_bwd.restype = c_int
-    L.stts_upsample2.argtypes = [c_vp, c_int, c_int, c_int, c_vp, c_vp]
-    L.stts_upsample2.restype = c_int
-    L.stts_upsample2_bwd.argtypes = [c_vp, c_int, c_int, c_int, c_vp, c_vp]
-    L.stts_upsample2_bwd.restype = c_int
-    L.stts_leaky_relu.argtypes = [c_vp, c_ll, ctypes.c_float, c_vp, c_vp]
-    L.stts_leaky_relu.restype = c_int
-    L.stts_leaky_relu_bwd.argtypes = [c_vp, c_vp, c_ll, ctypes.c_float, c_vp, c_vp]
-    L.stts_leaky_relu_bwd.restype = c_int
-    L.stts_conv1d_fwd_res.restype = c_int
-    L.stts_conv_transpose1d_workspace_bytes.argtypes = [c_int] * 9
-    L.stts_conv_transpose1d_workspace_bytes.restype = c_ll
-    L.stts_conv_transpose1d_fwd.argtypes = [c_int, c_vp, c_vp, c_vp] + [c_int] * 8 + [c_vp, c_vp, c_ll, c_vp]
-    L.stts_conv_transpose1d_fwd.restype = c_int
-    L.stts_conv_transpose1d_bwd.argtypes = [c_int, c_vp, c_vp, c_vp] + [c_int] * 8 + [c_vp, c_vp, c_vp, c_vp, c_ll,
-                                                                                      c_vp]
-    L.stts_conv_transpose1d_bwd.restype = c_int
-    L.stts_conv1d_bwd.argtypes = [c_int, c_vp, c_vp, c_vp] + [c_int] * 9 + [c_vp, c_vp, c_vp, c_vp, c_ll, c_vp]
-    L.stts_conv1d_bwd.restype = c_int
-    L.stts_weight_norm.argtypes = [c_vp, c_vp, c_int, c_int, c_vp, c_vp]
-    L.stts_weight_norm.restype = c_int
-    L.stts_adain_act_workspace_bytes.argtypes = [c_int, c_int, c_int]
-    L.stts_adain_act_workspace_bytes.restype = c_ll
-    L.stts_adain_act_fwd.argtypes = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_ll, c_vp]
-    L.stts_adain_act_fwd.restype = c_int
-    L.stts_adain_act_bwd.argtypes = [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp,
-                                     c_vp, c_ll, c_vp]
-    L.stts_adain_act_bwd.restype = c_int
-    L.stts_linear_fwd.argtypes = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp]
-    L.stts_linear_fwd.restype = c_int
-    L.stts_linear_bwd.argtypes = [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]
-    L.stts_linear_bwd.restype = c_int
-    L.stts_weight_norm_bwd.argtypes = [c_vp, c_vp, c_vp, c_int, c_int, c_vp, c_vp, c_vp]
-    L.stts_weight_norm_bwd.restype = c_int
-    L.stts_mrstft_workspace_bytes.argtypes = [c_int, c_ll, ctypes.POINTER(c_int), c_int, c_int]
-    L.stts_mrstft_workspace_bytes.restype = c_ll
-    L.stts_mrstft_loss.argtypes = [c_vp, c_vp, c_int, c_ll, c_ll, ctypes.POINTER(c_int), ctypes.POINTER(c_int),
-                                   ctypes.POINTER(c_int), c_int, c_int, c_int, c_vp, c_vp, c_ll, c_vp]
-    L.stts_mrstft_loss.restype = c_int
-    L.stts_mel_frames.argtypes = [c_ll]
-    L.stts_mel_frames.restype = c_ll
-    L.stts_mel_workspace_bytes.argtypes = []
-    L.stts_mel_workspace_bytes.restype = c_ll
-    L.stts_wave_preprocess.argtypes = [c_vp, c_int, c_ll, c_ll, c_vp, c_vp, c_ll, c_vp]
-    L.stts_wave_preprocess.restype = c_int
-    L.stts_error_string.argtypes = [c_int]
-    L.stts_error_string.restype = ctypes.c_char_p
-    L.stts_profile_enable.argtypes = [c_int]
-    L.stts_profile_enable.restype = c_int
-    L.stts_profile_read.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_ll),
-                                    ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
-    L.stts_profile_read.restype = c_int
-    L.stts_profile_launch.argtypes = [c_ll, ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_double)]
-    L.stts_profile_launch.restype = c_int
-    L.stts_set_option.argtypes = [c_int, c_int]
-    L.stts_set_option.restype = c_int
-    L.stts_get_option.argtypes = [c_int]
-    L.stts_get_option.restype = c_int
-    L.stts_set_debug_buffer.argtypes = [c_vp]
-    L.stts_set_debug_buffer.restype = c_int
+    for name, (args, res) in SIGNATURES.items():
+        fn = getattr(L, name, None)
+        if fn is None:
+            raise RuntimeError(f"{LIB_PATH} does not export {name} (include/*.h declares it): rebuild the library")
+        fn.argtypes, fn.restype = args, res
     _LIB = L
     if os.environ.get("STTS_OPTS"):
         for k, v in OPT_DEFAULTS.items():
@@ -180,8 +61,6 @@ OPT_RESCONV = 1
 OPT_GRID_CAP = 2
 OPT_DEBUG = 4
 OPT_STATS_SLOTS = 5
-
-
 OPT_SMALL_TILES = 6
 OPT_BIGCONV = 7
 OPT_HEAD = 8

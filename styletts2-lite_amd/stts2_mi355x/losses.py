@@ -19,9 +19,9 @@ import ctypes
 import torch
 from torch import nn
 
-from .engine import _ptr, _require_device, _stream, check
+from .engine import _ptr, _require_device, _stream, check, lib
 from .engine import log_norm  # noqa: F401  (utils.py:48-53, the N_real target of train.py:262)
-from .training import _f32, _tl, _ws
+from .training import _f32, _workspace, _ws
 
 GAN_FEATURE, GAN_GEN, GAN_DISC, GAN_TPRLS = 0, 1, 2, 3
 
@@ -53,11 +53,11 @@ class _GanFn(torch.autograd.Function):
         for i, k in enumerate(kinds):
             a, b = ts[2 * i], ts[2 * i + 1]
             terms[i] = _GanTerm(a.data_ptr(), b.data_ptr(), a.numel(), int(k))
-        nb = _tl().stts_gan_workspace_bytes(n)
+        nb = lib().stts_gan_workspace_bytes(n)
         check(int(nb) if nb < 0 else 0, "stts_gan_workspace_bytes")
         ws = _ws(nb, ts[0].device)
         loss = torch.empty(1, dtype=torch.float64, device=ts[0].device)
-        check(_tl().stts_gan_loss(terms, n, _ptr(loss), _ptr(ws), int(nb), _stream()), "stts_gan_loss")
+        check(lib().stts_gan_loss(terms, n, _ptr(loss), _ptr(ws), int(nb), _stream()), "stts_gan_loss")
         ctx.save_for_backward(*ts)
         ctx.kinds, ctx.ws, ctx.nb = kinds, ws, int(nb)
         return loss[0].to(torch.float32)
@@ -81,7 +81,7 @@ class _GanFn(torch.autograd.Function):
             db[i] = gb.data_ptr() if gb is not None else None
             grads += [ga, gb]
         g = _f32(go.reshape(1))
-        check(_tl().stts_gan_loss_bwd(terms, da, db, n, _ptr(g), _ptr(ctx.ws), ctx.nb, _stream()),
+        check(lib().stts_gan_loss_bwd(terms, da, db, n, _ptr(g), _ptr(ctx.ws), ctx.nb, _stream()),
               "stts_gan_loss_bwd")
         return (None, *grads)
 
@@ -177,11 +177,9 @@ class _MrstftFn(torch.autograd.Function):
         ffts, hops, wins = arr(mod.fft_sizes), arr(mod.hop_sizes), arr(mod.win_lengths)
         xc, yc = _f32(x2), _f32(y2)
         dev = xc.device
-        nb = _tl().stts_mrstft_workspace_bytes(B, L, hops, n, mod.n_mels)
-        check(int(nb) if nb < 0 else 0, "stts_mrstft_workspace_bytes")
-        ws = _ws(nb, dev)
+        ws, nb = _workspace("stts_mrstft_workspace_bytes", dev, B, L, hops, n, mod.n_mels)
         loss = torch.empty(1, dtype=torch.float64, device=dev)
-        check(_tl().stts_mrstft_loss(_ptr(xc), _ptr(yc), B, L, L, ffts, hops, wins, n, mod.sample_rate, mod.n_mels,
+        check(lib().stts_mrstft_loss(_ptr(xc), _ptr(yc), B, L, L, ffts, hops, wins, n, mod.sample_rate, mod.n_mels,
                                      _ptr(loss), _ptr(ws), int(nb), _stream()), "stts_mrstft_loss")
         ctx.save_for_backward(xc, yc)
         ctx.mod = mod
@@ -200,12 +198,10 @@ class _MrstftFn(torch.autograd.Function):
         n = len(mod.fft_sizes)
         arr = lambda v: (ctypes.c_int * n)(*[int(t) for t in v])  # noqa: E731
         ffts, hops, wins = arr(mod.fft_sizes), arr(mod.hop_sizes), arr(mod.win_lengths)
-        nb = _tl().stts_mrstft_bwd_workspace_bytes(B, L, ffts, hops, wins, n, mod.n_mels)
-        check(int(nb) if nb < 0 else 0, "stts_mrstft_bwd_workspace_bytes")
-        ws = _ws(nb, xc.device)
+        ws, nb = _workspace("stts_mrstft_bwd_workspace_bytes", xc.device, B, L, ffts, hops, wins, n, mod.n_mels)
         dx = torch.empty_like(xc)
         g = _f32(go.reshape(1))
-        check(_tl().stts_mrstft_loss_bwd(_ptr(xc), _ptr(yc), B, L, L, ffts, hops, wins, n, mod.sample_rate,
+        check(lib().stts_mrstft_loss_bwd(_ptr(xc), _ptr(yc), B, L, L, ffts, hops, wins, n, mod.sample_rate,
                                          mod.n_mels, _ptr(g), _ptr(dx), _ptr(ws), int(nb), _stream()),
               "stts_mrstft_loss_bwd")
         return dx, None, None
@@ -244,7 +240,7 @@ class _SmoothL1Fn(torch.autograd.Function):
         if xc.shape != yc.shape:
             raise ValueError(f"smooth_l1_loss: {tuple(xc.shape)} vs {tuple(yc.shape)}")
         loss = torch.empty(1, dtype=torch.float64, device=xc.device)
-        check(_tl().stts_smooth_l1_loss(_ptr(xc), _ptr(yc), xc.numel(), _ptr(loss), _stream()), "stts_smooth_l1_loss")
+        check(lib().stts_smooth_l1_loss(_ptr(xc), _ptr(yc), xc.numel(), _ptr(loss), _stream()), "stts_smooth_l1_loss")
         ctx.save_for_backward(xc, yc)
         return loss[0].to(torch.float32)
 
@@ -255,7 +251,7 @@ class _SmoothL1Fn(torch.autograd.Function):
         gd = _f32(g.reshape(1))
         dx = torch.empty_like(xc) if nx else None
         dy = torch.empty_like(yc) if ny else None
-        check(_tl().stts_smooth_l1_loss_bwd(_ptr(xc), _ptr(yc), xc.numel(), _ptr(gd), _ptr(dx), _ptr(dy), _stream()),
+        check(lib().stts_smooth_l1_loss_bwd(_ptr(xc), _ptr(yc), xc.numel(), _ptr(gd), _ptr(dx), _ptr(dy), _stream()),
               "stts_smooth_l1_loss_bwd")
         return dx, dy
 

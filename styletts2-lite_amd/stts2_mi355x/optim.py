@@ -16,8 +16,7 @@ from functools import reduce
 import torch
 from torch.autograd.graph import increment_version
 
-from .engine import _require_device, _stream, check
-from .training import _tl
+from .engine import _require_device, _stream, check, lib
 
 
 class _AdamWTensor(ctypes.Structure):
@@ -105,7 +104,7 @@ class AdamW(torch.optim.Optimizer):
         arr = (_AdamWTensor * len(items))()
         for i, (p, g, m, v) in enumerate(items):
             arr[i] = _AdamWTensor(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel())
-        check(_tl().stts_adamw_step_dev(arr, len(items), ctypes.c_double(group["lr"]), ctypes.c_double(beta1),
+        check(lib().stts_adamw_step_dev(arr, len(items), ctypes.c_double(group["lr"]), ctypes.c_double(beta1),
                                         ctypes.c_double(beta2), ctypes.c_double(group["eps"]),
                                         ctypes.c_double(group["weight_decay"]), ctypes.c_void_p(dev.data_ptr()),
                                         _stream()), "stts_adamw_step_dev")
@@ -157,7 +156,7 @@ class AdamW(torch.optim.Optimizer):
                 arr = (_AdamWTensor * len(items))()
                 for i, (p, g, m, v) in enumerate(items):
                     arr[i] = _AdamWTensor(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel())
-                check(_tl().stts_adamw_step(arr, len(items), ctypes.c_double(group["lr"]), ctypes.c_double(beta1),
+                check(lib().stts_adamw_step(arr, len(items), ctypes.c_double(group["lr"]), ctypes.c_double(beta1),
                                             ctypes.c_double(beta2), ctypes.c_double(group["eps"]),
                                             ctypes.c_double(group["weight_decay"]), step, _stream()),
                       "stts_adamw_step")

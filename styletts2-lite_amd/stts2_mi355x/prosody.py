@@ -23,58 +23,17 @@ from torch.nn.utils.rnn import PackedSequence, pack_padded_sequence, pad_packed_
 
 from .engine import _ptr, _stream, check, lib
 
-c_int, c_ll, c_vp, c_float = ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_float
-_BOUND = False
-
-
-def _L():
-    global _BOUND
-    L = lib()
-    if not _BOUND:
-        L.stts_frames_gemm.argtypes = [c_vp, c_ll, c_ll, c_ll, c_int, c_int, c_int, c_vp, c_ll, c_ll, c_ll, c_ll,
-                                       c_int, c_int, c_int, c_vp, c_vp, c_vp, c_ll, c_ll, c_ll, c_int, c_vp]
-        L.stts_frames_gemm.restype = c_int
-        L.stts_frames_gemm_ws.argtypes = [c_vp, c_ll, c_ll, c_ll, c_int, c_int, c_int, c_vp, c_ll, c_ll, c_ll, c_ll,
-                                          c_int, c_int, c_int, c_vp, c_vp, c_vp, c_ll, c_ll, c_ll, c_int, c_vp, c_ll,
-                                          c_vp]
-        L.stts_frames_gemm_ws.restype = c_int
-        L.stts_bilstm_workspace_bytes.argtypes = [c_int, c_int, c_int]
-        L.stts_bilstm_workspace_bytes.restype = c_ll
-        L.stts_bilstm_fwd.argtypes = [c_vp, c_ll, c_ll, c_ll, c_int, c_int, c_int, c_vp, ctypes.POINTER(c_vp), c_int,
-                                      c_vp, c_vp, c_vp, c_vp, c_ll, c_vp]
-        L.stts_bilstm_fwd.restype = c_int
-        L.stts_set_lstm_group.argtypes = [c_int]
-        L.stts_set_lstm_group.restype = c_int
-        L.stts_bilstm_error_offset.argtypes = [c_int, c_int, c_int]
-        L.stts_bilstm_error_offset.restype = c_ll
-        L.stts_set_bilstm_debug.argtypes = [c_int, c_int]
-        L.stts_set_bilstm_debug.restype = c_int
-        L.stts_row_norm.argtypes = [c_vp, c_ll, c_ll, c_ll, c_int, c_int, c_int, c_int, c_vp, c_vp, c_ll, c_float,
-                                    c_int, c_float, c_vp, c_vp, c_int, c_vp, c_ll, c_ll, c_vp]
-        L.stts_row_norm.restype = c_int
-        L.stts_embedding.argtypes = [c_vp, c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_vp]
-        L.stts_embedding.restype = c_int
-        L.stts_weight_norm.argtypes = [c_vp, c_vp, c_int, c_int, c_vp, c_vp]
-        L.stts_weight_norm.restype = c_int
-        L.stts_durations.argtypes = [c_vp, c_ll, c_ll, c_int, c_int, c_int, c_vp, c_vp, c_float, c_float, c_float,
-                                     c_vp, c_vp, c_vp, c_vp, c_vp]
-        L.stts_durations.restype = c_int
-        L.stts_expand_frames.argtypes = [c_vp, c_ll, c_ll, c_ll, c_int, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp]
-        L.stts_expand_frames.restype = c_int
-        _BOUND = True
-    return L
-
 
 def set_lstm_group(bg: int) -> None:
     """BiLSTM recurrence kernel: 0 = automatic, -1 = cooperative (H = 256), 1 / 2 / 4 = utterances per
     workgroup of the per-workgroup kernel (A/B testing)."""
-    check(_L().stts_set_lstm_group(int(bg)), "stts_set_lstm_group")
+    check(lib().stts_set_lstm_group(int(bg)), "stts_set_lstm_group")
 
 
 def set_bilstm_debug(spin_limit: int = 0, drop: bool = False) -> None:
     """Testing hook of the cooperative recurrence (stts_set_bilstm_debug): waits give up after
     `spin_limit` polls (0 = the default bound) and, with `drop`, one workgroup never publishes."""
-    check(_L().stts_set_bilstm_debug(int(spin_limit), 1 if drop else 0), "stts_set_bilstm_debug")
+    check(lib().stts_set_bilstm_debug(int(spin_limit), 1 if drop else 0), "stts_set_bilstm_debug")
 
 
 # device error words of BiLSTM launches not yet read by the host (stts_bilstm_error_offset)
@@ -119,8 +78,8 @@ def frames_gemm(x, xs, B, Tin, Cin, w, wst, N, K, pad, bias, bias2, y, ys, Tout)
     tiles = ((Tout + 63) // 64) * ((N + 63) // 64) * B
     elems = 16 * B * Tout * N if tiles < 128 and Cin * K >= 256 else 0
     ws = torch.empty(elems, dtype=torch.float32, device=y.device) if elems else None
-    check(_L().stts_frames_gemm_ws(_ptr(x), *xs, B, Tin, Cin, _ptr(w), *wst, N, K, pad, _ptr(bias), _ptr(bias2),
-                                   _ptr(y), *ys, Tout, _ptr(ws), elems * 4, _stream()), "stts_frames_gemm_ws")
+    check(lib().stts_frames_gemm_ws(_ptr(x), *xs, B, Tin, Cin, _ptr(w), *wst, N, K, pad, _ptr(bias), _ptr(bias2),
+                                    _ptr(y), *ys, Tout, _ptr(ws), elems * 4, _stream()), "stts_frames_gemm_ws")
 
 
 def matmul(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
@@ -157,16 +116,16 @@ def row_norm(x, C, mode, gamma=None, beta=None, gb_sb=0, eps=1e-5, slope=None, l
     B, T = x.shape[0], x.shape[1]
     E = 0 if extra is None else extra.shape[1]
     y = torch.empty(B, T, C + E, dtype=torch.float32, device=x.device)
-    check(_L().stts_row_norm(_ptr(x), x.stride(0), x.stride(1), x.stride(2), B, T, C, mode, _ptr(gamma), _ptr(beta),
-                             gb_sb, eps, 0 if slope is None else 1, 0.0 if slope is None else slope, _ptr(lengths),
-                             _ptr(extra), E, _ptr(y), y.stride(0), y.stride(1), _stream()), "stts_row_norm")
+    check(lib().stts_row_norm(_ptr(x), x.stride(0), x.stride(1), x.stride(2), B, T, C, mode, _ptr(gamma), _ptr(beta),
+                              gb_sb, eps, 0 if slope is None else 1, 0.0 if slope is None else slope, _ptr(lengths),
+                              _ptr(extra), E, _ptr(y), y.stride(0), y.stride(1), _stream()), "stts_row_norm")
     return y
 
 
 def weight_norm_fold(g: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
     w = torch.empty_like(v)
     d0 = v.shape[0]
-    check(_L().stts_weight_norm(_ptr(g), _ptr(v), d0, v.numel() // d0, _ptr(w), _stream()), "stts_weight_norm")
+    check(lib().stts_weight_norm(_ptr(g), _ptr(v), d0, v.numel() // d0, _ptr(w), _stream()), "stts_weight_norm")
     return w
 
 
@@ -185,9 +144,9 @@ def durations(logits, lengths=None, z=None, mix=0.0, prev_mean=0.0, speed=1.0):
     pred = torch.empty(B, T, dtype=torch.int32, device=dev)
     total = torch.empty(B, dtype=torch.int32, device=dev)
     dmean = torch.empty(B, dtype=torch.float32, device=dev)
-    check(_L().stts_durations(_ptr(logits), logits.stride(0), logits.stride(1), B, T, K, _ptr(ln), _ptr(z),
-                              float(mix), float(prev_mean), float(speed), _ptr(dur), _ptr(pred), _ptr(total),
-                              _ptr(dmean), _stream()), "stts_durations")
+    check(lib().stts_durations(_ptr(logits), logits.stride(0), logits.stride(1), B, T, K, _ptr(ln), _ptr(z),
+                               float(mix), float(prev_mean), float(speed), _ptr(dur), _ptr(pred), _ptr(total),
+                               _ptr(dmean), _stream()), "stts_durations")
     return dur, pred, total, dmean
 
 
@@ -199,8 +158,8 @@ def expand_frames(src_btc: torch.Tensor, pred: torch.Tensor, Fmax: int) -> torch
     pred = pred.to(torch.int32).contiguous()
     y = torch.empty(B, C, Fmax, dtype=torch.float32, device=src_btc.device)
     ftok = torch.empty(B, max(Fmax, 1), dtype=torch.int32, device=src_btc.device)
-    check(_L().stts_expand_frames(_ptr(src_btc), *src_btc.stride(), B, T, C, _ptr(pred), Fmax, _ptr(ftok), _ptr(y),
-                                  _stream()), "stts_expand_frames")
+    check(lib().stts_expand_frames(_ptr(src_btc), *src_btc.stride(), B, T, C, _ptr(pred), Fmax, _ptr(ftok), _ptr(y),
+                                   _stream()), "stts_expand_frames")
     return y
 
 
@@ -250,8 +209,8 @@ class LSTM(nn.LSTM):
         params = [self.weight_ih_l0, self.weight_hh_l0, self.bias_ih_l0, self.bias_hh_l0, self.weight_ih_l0_reverse,
                   self.weight_hh_l0_reverse, self.bias_ih_l0_reverse, self.bias_hh_l0_reverse]
         params = [_on_device(p.detach(), "LSTM parameter").contiguous() for p in params]
-        arr = (c_vp * 8)(*[p.data_ptr() for p in params])
-        L = _L()
+        arr = (ctypes.c_void_p * 8)(*[p.data_ptr() for p in params])
+        L = lib()
         nb = int(L.stts_bilstm_workspace_bytes(B, T, H))
         ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=x.device)
         y = torch.empty(B, T, 2 * H, dtype=torch.float32, device=x.device)
@@ -344,8 +303,8 @@ class TextEncoder(nn.Module):
         h = torch.empty(B, T, C, dtype=torch.float32, device=dev)
         err = None if host_checked else torch.zeros(1, dtype=torch.int32, device=dev)
         emb = _on_device(self.embedding.weight.detach(), "embedding").contiguous()
-        check(_L().stts_embedding(_ptr(tok), B, T, _ptr(emb), self.n_symbols, C, _ptr(ln), _ptr(h), _ptr(err),
-                                  _stream()), "stts_embedding")
+        check(lib().stts_embedding(_ptr(tok), B, T, _ptr(emb), self.n_symbols, C, _ptr(ln), _ptr(h), _ptr(err),
+                                   _stream()), "stts_embedding")
         for blk in self.cnn:
             conv, ln_mod = blk[0], blk[1]
             w = self._folded(conv)

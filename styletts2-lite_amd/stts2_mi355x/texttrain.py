@@ -20,36 +20,11 @@ the fused inference kernels.  Tensors live on the HIP device; there is no CPU fa
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
-from .engine import _ptr, _require_device, _stream, check
-from .prosody import _L as _pl, _lengths, frames_gemm
-from .training import _c, _tl, _ws, conv1d_frames, dropout, linear, weight_norm
-
-_BOUND = False
-
-
-def _lib():
-    global _BOUND
-    L = _tl()
-    _pl()
-    if not _BOUND:
-        vp, i, ll, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float
-        sig = {
-            "stts_row_norm_bwd_workspace_bytes": ([i, i, i], ll),
-            "stts_row_norm_bwd": ([vp, ll, ll, ll, i, i, i, i, vp, vp, ll, f, i, f, vp, vp, ll, ll, i, vp, vp, vp, vp, vp,
-                                   vp, ll, vp], i),
-            "stts_embedding_bwd": ([vp, i, i, vp, vp, ll, ll, i, i, vp, vp], i),
-            "stts_dur_losses_workspace_bytes": ([i], ll),
-            "stts_dur_losses": ([vp, ll, ll, i, i, i, vp, vp, ll, vp, vp, vp, vp, vp, ll, vp], i),
-        }
-        for name, (args, res) in sig.items():
-            fn = getattr(L, name)
-            fn.argtypes, fn.restype = args, res
-        _BOUND = True
-    return L
+from .engine import _ptr, _require_device, _stream, check, lib
+from .prosody import _lengths, frames_gemm
+from .training import _c, _workspace, conv1d_frames, dropout, linear, weight_norm
 
 
 def needs_grad(module, *inputs) -> bool:
@@ -70,7 +45,7 @@ class _EmbeddingFn(torch.autograd.Function):
         wc = _c(weight)
         h = torch.empty(B, T, C, dtype=torch.float32, device=weight.device)
         err = torch.zeros(1, dtype=torch.int32, device=weight.device)
-        check(_pl().stts_embedding(_ptr(tok), B, T, _ptr(wc), n_sym, C, _ptr(ln), _ptr(h), _ptr(err), _stream()),
+        check(lib().stts_embedding(_ptr(tok), B, T, _ptr(wc), n_sym, C, _ptr(ln), _ptr(h), _ptr(err), _stream()),
               "stts_embedding")
         ctx.save_for_backward(tok, ln if ln is not None else torch.empty(0))
         ctx.has_ln, ctx.shape = ln is not None, (n_sym, C)
@@ -85,8 +60,8 @@ class _EmbeddingFn(torch.autograd.Function):
         B, T = tok.shape
         dhc = _c(dh)
         dW = torch.empty(n_sym, C, dtype=torch.float32, device=dh.device)
-        check(_lib().stts_embedding_bwd(_ptr(tok), B, T, _ptr(ln), _ptr(dhc), dhc.stride(0), dhc.stride(1), n_sym, C,
-                                        _ptr(dW), _stream()), "stts_embedding_bwd")
+        check(lib().stts_embedding_bwd(_ptr(tok), B, T, _ptr(ln), _ptr(dhc), dhc.stride(0), dhc.stride(1), n_sym, C,
+                                       _ptr(dW), _stream()), "stts_embedding_bwd")
         return dW, None, None
 
 
@@ -106,7 +81,7 @@ class _RowNormFn(torch.autograd.Function):
         ex = _c(extra) if extra is not None else None
         y = torch.empty(B, T, C + E, dtype=torch.float32, device=x.device)
         gb_sb = g.stride(0) if mode == 1 else 0
-        check(_pl().stts_row_norm(_ptr(xc), xc.stride(0), xc.stride(1), xc.stride(2), B, T, C, mode, _ptr(g), _ptr(bt),
+        check(lib().stts_row_norm(_ptr(xc), xc.stride(0), xc.stride(1), xc.stride(2), B, T, C, mode, _ptr(g), _ptr(bt),
                                   gb_sb, eps, 0 if slope is None else 1, 0.0 if slope is None else slope, _ptr(ln),
                                   _ptr(ex), E, _ptr(y), y.stride(0), y.stride(1), _stream()), "stts_row_norm")
         ctx.save_for_backward(xc, *(t if t is not None else torch.empty(0) for t in (g, bt, ln)))
@@ -126,9 +101,8 @@ class _RowNormFn(torch.autograd.Function):
         dbeta = torch.empty(C, dtype=torch.float32, device=dy.device) if (mode == 0 and need[2]) else None
         dgb = torch.empty(B, 2 * C, dtype=torch.float32, device=dy.device) if (mode == 1 and need[3]) else None
         dex = torch.empty(B, E, dtype=torch.float32, device=dy.device) if (E and need[4]) else None
-        L = _lib()
-        nb = int(L.stts_row_norm_bwd_workspace_bytes(B, T, C))
-        ws = _ws(nb, dy.device)
+        L = lib()
+        ws, nb = _workspace("stts_row_norm_bwd_workspace_bytes", dy.device, B, T, C)
         check(L.stts_row_norm_bwd(_ptr(xc), xc.stride(0), xc.stride(1), xc.stride(2), B, T, C, mode,
                                   _ptr(g if mode != 2 else None), _ptr(bt if mode == 0 else None), gb_sb, eps,
                                   0 if slope is None else 1, 0.0 if slope is None else slope, _ptr(ln), _ptr(dyc),
@@ -195,9 +169,8 @@ class _DurLossFn(torch.autograd.Function):
         dc = _c(d)
         gt = _c(d_gt.to(torch.float32))
         loss = torch.empty(2, dtype=torch.float64, device=d.device)
-        L = _lib()
-        nb = int(L.stts_dur_losses_workspace_bytes(B))
-        ws = _ws(nb, d.device)
+        L = lib()
+        ws, nb = _workspace("stts_dur_losses_workspace_bytes", d.device, B)
         check(L.stts_dur_losses(_ptr(dc), dc.stride(0), dc.stride(1), B, T, K, _ptr(ln), _ptr(gt), gt.stride(0),
                                 _ptr(loss), None, None, None, _ptr(ws), nb, _stream()), "stts_dur_losses")
         ctx.save_for_backward(dc, gt, ln if ln is not None else torch.empty(0))
@@ -215,9 +188,8 @@ class _DurLossFn(torch.autograd.Function):
         gc = _c(g_ce.reshape(1)) if g_ce is not None else None
         dz = torch.empty(B, T, K, dtype=torch.float32, device=dc.device)
         loss = torch.empty(2, dtype=torch.float64, device=dc.device)
-        L = _lib()
-        nb = int(L.stts_dur_losses_workspace_bytes(B))
-        ws = _ws(nb, dc.device)
+        L = lib()
+        ws, nb = _workspace("stts_dur_losses_workspace_bytes", dc.device, B)
         check(L.stts_dur_losses(_ptr(dc), dc.stride(0), dc.stride(1), B, T, K, _ptr(ln), _ptr(gt), gt.stride(0),
                                 _ptr(loss), _ptr(dz), _ptr(gd), _ptr(gc), _ptr(ws), nb, _stream()), "stts_dur_losses")
         return dz, None, None

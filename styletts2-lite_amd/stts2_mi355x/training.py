@@ -24,7 +24,6 @@ from .engine import _ptr, _require_device, _stream, check, lib
 
 # bf16x3: the split-operand mode (fp32 frames, forward / dx operands as bf16 hi + lo, three MFMAs; dw in fp32)
 _DT = {"fp32": 0, "bf16": 1, "bf16x3": 2}
-_TRAIN_READY = False
 # algorithmic conv work of the autograd path (measurement: tools/bench_train_step.py): 2 B Lq Cout Cin K flops per
 # conv forward, the same again per dx and per dw (the transposed conv: 2 B Lin Cin Cout K)
 CONV_FLOPS = {"on": False, "fwd": 0.0, "bwd": 0.0}
@@ -35,83 +34,16 @@ def _count(kind, flops):
         CONV_FLOPS[kind] += flops
 
 
-def _tl():
-    """lib() with the argument types of the training-step entry points (include/stts2_train.h)."""
-    global _TRAIN_READY
-    L = lib()
-    if _TRAIN_READY:
-        return L
-    vp, i, ll, f, d, ull = (ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float, ctypes.c_double,
-                           ctypes.c_ulonglong)
-    sig = {
-        "stts_snake_workspace_bytes": ([i, i, i], ll),
-        "stts_snake_fwd": ([vp, vp, i, i, i, vp, vp], i),
-        "stts_snake_bwd": ([vp, vp, vp, i, i, i, vp, vp, vp, ll, vp], i),
-        "stts_tanh_fwd": ([vp, ll, vp, vp], i),
-        "stts_tanh_bwd": ([vp, vp, ll, vp, vp], i),
-        "stts_sum_div": ([vp, i, ll, f, vp, vp], i),
-        "stts_div": ([vp, ll, f, vp, vp], i),
-        "stts_source_workspace_bytes": ([i, i], ll),
-        "stts_source_fwd": ([vp, vp, vp, vp, ull, ll, i, i, i, vp, vp, vp, ll, vp], i),
-        "stts_source_bwd": ([vp, vp, vp, i, ll, vp, vp, vp, ll, vp], i),
-        "stts_box_smooth_fwd": ([vp, i, i, i, vp, vp], i),
-        "stts_box_smooth_bwd": ([vp, i, i, i, vp, vp], i),
-        "stts_time_expand3": ([vp, i, i, i, i, vp, vp], i),
-        "stts_time_expand3_bwd": ([vp, i, i, i, i, vp, vp], i),
-        "stts_stft_mag_workspace_bytes": ([i, ll, i, i, i], ll),
-        "stts_stft_mag_fwd": ([vp, i, ll, ll, i, i, i, vp, vp, vp], i),
-        "stts_stft_mag_bwd": ([vp, vp, i, ll, i, i, i, vp, vp, ll, vp], i),
-        "stts_mrstft_bwd_workspace_bytes": ([i, ll, vp, vp, vp, i, i], ll),
-        "stts_mrstft_loss_bwd": ([vp, vp, i, ll, ll, vp, vp, vp, i, i, i, vp, vp, vp, ll, vp], i),
-        "stts_gan_workspace_bytes": ([i], ll),
-        "stts_gan_loss": ([vp, i, vp, vp, ll, vp], i),
-        "stts_gan_loss_bwd": ([vp, vp, vp, i, vp, vp, ll, vp], i),
-        "stts_adamw_step": ([vp, i, d, d, d, d, d, ll, vp], i),
-        "stts_adamw_step_dev": ([vp, i, d, d, d, d, d, vp, vp], i),
-        "stts_source_fwd_seed_dev": ([vp, vp, vp, vp, vp, ll, i, i, i, vp, vp, vp, ll, vp], i),
-        "stts_bilstm_workspace_bytes": ([i, i, i], ll),
-        "stts_bilstm_fwd_train": ([vp, ll, ll, ll, i, i, i, vp, vp, i, vp, vp, vp, ll, vp], i),
-        "stts_bilstm_bwd_workspace_bytes": ([i, i, i, i], ll),
-        "stts_bilstm_bwd": ([vp, i, i, i, vp, vp, i, vp, vp, vp, vp, vp, vp, ll, vp], i),
-        "stts_dropout": ([vp, ll, f, ull, vp, vp], i),
-        "stts_dropout_mask": ([vp, vp, ll, f, vp, vp], i),
-        "stts_rowexp_fwd": ([vp, i, i, i, i, i, i, vp, vp], i),
-        "stts_rowexp_bwd": ([vp, i, i, i, i, i, i, vp, vp], i),
-        "stts_dwconv2d_s2_fwd": ([vp, vp, vp, i, i, i, i, vp, vp], i),
-        "stts_dwconv2d_s2_workspace_bytes": ([i], ll),
-        "stts_dwconv2d_s2_bwd": ([vp, vp, vp, i, i, i, i, vp, vp, vp, vp, ll, vp], i),
-        "stts_avgpool2_fwd": ([vp, i, i, i, i, vp, vp], i),
-        "stts_avgpool2_bwd": ([vp, i, i, i, i, vp, vp], i),
-        "stts_spatial_mean_fwd": ([vp, i, i, i, vp, vp], i),
-        "stts_spatial_mean_bwd": ([vp, i, i, i, vp, vp], i),
-        "stts_smooth_l1_loss": ([vp, vp, ll, vp, vp], i),
-        "stts_smooth_l1_loss_bwd": ([vp, vp, ll, vp, vp, vp, vp], i),
-        "stts_dwconv1d_fwd": ([vp, vp, vp, i, i, i, i, vp, vp], i),
-        "stts_dwconv1d_bwd_workspace_bytes": ([i, i, i, i], ll),
-        "stts_dwconv1d_bwd": ([vp, vp, vp, i, i, i, i, vp, vp, vp, vp, ll, vp], i),
-        "stts_gelu_fwd": ([vp, ll, vp, vp], i),
-        "stts_gelu_bwd": ([vp, vp, ll, vp, vp], i),
-        "stts_layer_scale_res_fwd": ([vp, vp, vp, i, i, i, vp, vp], i),
-        "stts_layer_scale_res_bwd_workspace_bytes": ([i, i, i], ll),
-        "stts_layer_scale_res_bwd": ([vp, vp, vp, i, i, i, vp, vp, vp, ll, vp], i),
-        "stts_istft_head_workspace_bytes": ([i, i, i, i], ll),
-        "stts_istft_head_fwd": ([vp, vp, i, i, i, i, vp, vp, ll, vp], i),
-        "stts_istft_head_bwd": ([vp, vp, vp, i, i, i, i, vp, vp, ll, vp], i),
-        "stts_cstft_fwd": ([vp, vp, vp, i, i, i, i, vp, vp], i),
-        "stts_padl_add_fwd": ([vp, vp, i, i, i, vp, vp], i),
-        "stts_padl_add_bwd": ([vp, i, i, i, vp, vp], i),
-        "stts_cistft_head_fwd": ([vp, vp, vp, i, i, i, i, vp, vp], i),
-        "stts_cistft_head_bwd": ([vp, vp, vp, vp, i, i, i, i, vp, vp], i),
-    }
-    for name, (args, res) in sig.items():
-        fn = getattr(L, name)
-        fn.argtypes, fn.restype = args, res
-    _TRAIN_READY = True
-    return L
-
-
 def _ws(nbytes: int, device) -> torch.Tensor:
     return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+
+
+def _workspace(query: str, device, *args):
+    """(buffer, bytes) for a kernel whose size query is lib().<query>(*args); a negative size is the query's
+    STTS_E* code for these arguments and raises."""
+    nbytes = int(getattr(lib(), query)(*args))
+    check(nbytes if nbytes < 0 else 0, query)
+    return _ws(nbytes, device), nbytes
 
 
 def out_length(Lin: int, K: int, stride: int, pad: int, dil: int) -> int:
@@ -133,9 +65,7 @@ class _Conv1dFn(torch.autograd.Function):
         xf = x.detach().to(torch.float32).contiguous()
         wc = w.detach().to(torch.float32).contiguous()
         bc = bias.detach().to(torch.float32).contiguous() if bias is not None else None
-        nb = lib().stts_conv1d_fwd_workspace_bytes(dt, B, Lin, Cin, Cout, K, stride, dil, pad, Lq)
-        check(int(nb) if nb < 0 else 0, "stts_conv1d_fwd_workspace_bytes")
-        ws = _ws(nb, x.device)
+        ws, nb = _workspace("stts_conv1d_fwd_workspace_bytes", x.device, dt, B, Lin, Cin, Cout, K, stride, dil, pad, Lq)
         y = torch.empty(B, Lq, Cout, dtype=torch.float32, device=x.device)
         ctx.scale = float(scale)
         ctx.act = act
@@ -151,7 +81,7 @@ class _Conv1dFn(torch.autograd.Function):
                                         _ptr(y), _ptr(ws), int(nb), _stream()), "stts_conv1d_fwd")
             rc = res.detach().to(torch.float32).contiguous()
             xs = (ctypes.c_void_p * 2)(y.data_ptr(), rc.data_ptr())
-            check(_tl().stts_sum_div(xs, 2, y.numel(), ctypes.c_float(1.0 / scale), _ptr(y), _stream()),
+            check(lib().stts_sum_div(xs, 2, y.numel(), ctypes.c_float(1.0 / scale), _ptr(y), _stream()),
                   "stts_sum_div")
         elif res is not None or scale != 1.0:
             rc = res.detach().to(torch.float32).contiguous() if res is not None else None
@@ -181,9 +111,7 @@ class _Conv1dFn(torch.autograd.Function):
                                             _stream()), "stts_leaky_relu_bwd")
             dyf = dpre
         dev = dyf.device
-        nb = lib().stts_conv1d_bwd_workspace_bytes(dt, B, Lin, Cin, Cout, K, stride, dil, pad, Lq)
-        check(int(nb) if nb < 0 else 0, "stts_conv1d_bwd_workspace_bytes")
-        ws = _ws(nb, dev)
+        ws, nb = _workspace("stts_conv1d_bwd_workspace_bytes", dev, dt, B, Lin, Cin, Cout, K, stride, dil, pad, Lq)
         dx = torch.empty(B, Lin, Cin, dtype=torch.float32, device=dev) if need_x else None
         dw = torch.empty(Cout, Cin, K, dtype=torch.float32, device=dev) if need_w else None
         db = torch.empty(Cout, dtype=torch.float32, device=dev) if (need_b and has_bias) else None
@@ -287,9 +215,8 @@ class _ConvT1dFn(torch.autograd.Function):
         Lout = (Lin - 1) * stride - 2 * pad + K + out_pad
         dt = _DT[dtype]
         xf, wc, bc = _c(x), _c(w), _c(bias)
-        nb = lib().stts_conv_transpose1d_workspace_bytes(dt, B, Lin, Cin, Cout, K, stride, pad, Lout)
-        check(int(nb) if nb < 0 else 0, "stts_conv_transpose1d_workspace_bytes")
-        ws = _ws(nb, x.device)
+        ws, nb = _workspace("stts_conv_transpose1d_workspace_bytes", x.device, dt, B, Lin, Cin, Cout, K, stride, pad,
+                            Lout)
         y = torch.empty(B, Lout, Cout, dtype=torch.float32, device=x.device)
         check(lib().stts_conv_transpose1d_fwd(dt, _ptr(xf), _ptr(wc), _ptr(bc), B, Lin, Cin, Cout, K, stride, pad,
                                               Lout, _ptr(y), _ptr(ws), int(nb), _stream()),
@@ -305,8 +232,8 @@ class _ConvT1dFn(torch.autograd.Function):
         B, Lin, Cin, Cout, K, stride, pad, Lout, dt, has_bias = ctx.geo
         nx, nw, nbias = ctx.needs_input_grad[:3]
         dy = _c(gy)
-        nb = lib().stts_conv_transpose1d_workspace_bytes(dt, B, Lin, Cin, Cout, K, stride, pad, Lout)
-        ws = _ws(nb, dy.device)
+        ws, nb = _workspace("stts_conv_transpose1d_workspace_bytes", dy.device, dt, B, Lin, Cin, Cout, K, stride, pad,
+                            Lout)
         dx = torch.empty_like(xf) if nx else None
         dw = torch.empty_like(wc) if nw else None
         db = torch.empty(Cout, dtype=torch.float32, device=dy.device) if (nbias and has_bias) else None
@@ -375,9 +302,7 @@ class _AdaINActFn(torch.autograd.Function):
         _require_device()
         B, L, C = x.shape
         xc, gbc, ac = _c(x), _c(gb), _c(alpha.reshape(-1)) if alpha is not None else None
-        nb = lib().stts_adain_act_workspace_bytes(B, L, C)
-        check(int(nb) if nb < 0 else 0, "stts_adain_act_workspace_bytes")
-        ws = _ws(nb, x.device)
+        ws, nb = _workspace("stts_adain_act_workspace_bytes", x.device, B, L, C)
         y = torch.empty_like(xc)
         mr = torch.empty(B, C, 2, dtype=torch.float32, device=x.device)
         check(lib().stts_adain_act_fwd(_ptr(xc), _ptr(gbc), _ptr(ac), act, B, L, C, _ptr(y), _ptr(mr), _ptr(ws),
@@ -393,8 +318,7 @@ class _AdaINActFn(torch.autograd.Function):
         B, L, C = xc.shape
         dy = _c(dy)
         nx, ngb, na = ctx.needs_input_grad[:3]
-        nb = lib().stts_adain_act_workspace_bytes(B, L, C)
-        ws = _ws(nb, dy.device)
+        ws, nb = _workspace("stts_adain_act_workspace_bytes", dy.device, B, L, C)
         dx = torch.empty_like(xc) if nx else None
         dgb = torch.empty_like(gbc) if ngb else None
         da = torch.empty(C, dtype=torch.float32, device=dy.device) if (na and act == ACT_SNAKE) else None
@@ -522,8 +446,7 @@ class _PoolFn(torch.autograd.Function):
         dx = torch.empty_like(xc) if nx else None
         dw = torch.empty(C, 3, dtype=torch.float32, device=dy.device) if nw else None
         db = torch.empty(C, dtype=torch.float32, device=dy.device) if (nb_ and ctx.has_b) else None
-        nb = lib().stts_pool_workspace_bytes(B, Lin, C)
-        ws = _ws(nb, dy.device)
+        ws, nb = _workspace("stts_pool_workspace_bytes", dy.device, B, Lin, C)
         check(lib().stts_pool_bwd(_ptr(xc), _ptr(wc), _ptr(dy), B, Lin, C, _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws),
                                   int(nb), _stream()), "stts_pool_bwd")
         return dx, (dw.reshape(ctx.w_shape) if dw is not None else None), db
@@ -735,7 +658,7 @@ class _SnakeFn(torch.autograd.Function):
         B, L, C = x.shape
         xc, ac = _f32(x), _f32(alpha.reshape(-1))
         y = torch.empty_like(xc)
-        check(_tl().stts_snake_fwd(_ptr(xc), _ptr(ac), B, L, C, _ptr(y), _stream()), "stts_snake_fwd")
+        check(lib().stts_snake_fwd(_ptr(xc), _ptr(ac), B, L, C, _ptr(y), _stream()), "stts_snake_fwd")
         ctx.save_for_backward(xc, ac)
         ctx.a_shape = alpha.shape
         return y
@@ -748,9 +671,8 @@ class _SnakeFn(torch.autograd.Function):
         dyc = _f32(dy)
         dx = torch.empty_like(xc) if nx else None
         da = torch.empty(C, dtype=torch.float32, device=dyc.device) if na else None
-        nb = _tl().stts_snake_workspace_bytes(B, L, C)
-        ws = _ws(nb, dyc.device)
-        check(_tl().stts_snake_bwd(_ptr(xc), _ptr(ac), _ptr(dyc), B, L, C, _ptr(dx), _ptr(da), _ptr(ws), int(nb),
+        ws, nb = _workspace("stts_snake_workspace_bytes", dyc.device, B, L, C)
+        check(lib().stts_snake_bwd(_ptr(xc), _ptr(ac), _ptr(dyc), B, L, C, _ptr(dx), _ptr(da), _ptr(ws), int(nb),
                                    _stream()), "stts_snake_bwd")
         return dx, (da.reshape(ctx.a_shape) if da is not None else None)
 
@@ -765,7 +687,7 @@ class _TanhFn(torch.autograd.Function):
         _require_device()
         xc = _f32(x)
         y = torch.empty_like(xc)
-        check(_tl().stts_tanh_fwd(_ptr(xc), xc.numel(), _ptr(y), _stream()), "stts_tanh_fwd")
+        check(lib().stts_tanh_fwd(_ptr(xc), xc.numel(), _ptr(y), _stream()), "stts_tanh_fwd")
         ctx.save_for_backward(y)
         return y
 
@@ -774,7 +696,7 @@ class _TanhFn(torch.autograd.Function):
         (y,) = ctx.saved_tensors
         dyc = _f32(dy)
         dx = torch.empty_like(y)
-        check(_tl().stts_tanh_bwd(_ptr(y), _ptr(dyc), y.numel(), _ptr(dx), _stream()), "stts_tanh_bwd")
+        check(lib().stts_tanh_bwd(_ptr(y), _ptr(dyc), y.numel(), _ptr(dx), _stream()), "stts_tanh_bwd")
         return dx
 
 
@@ -794,7 +716,7 @@ class _SumDivFn(torch.autograd.Function):
                 raise ValueError(f"sum of tensors of shapes {[tuple(t.shape) for t in xc]}")
         y = torch.empty_like(xc[0])
         arr = (ctypes.c_void_p * len(xc))(*[x.data_ptr() for x in xc])
-        check(_tl().stts_sum_div(arr, len(xc), y.numel(), ctypes.c_float(div), _ptr(y), _stream()), "stts_sum_div")
+        check(lib().stts_sum_div(arr, len(xc), y.numel(), ctypes.c_float(div), _ptr(y), _stream()), "stts_sum_div")
         ctx.div, ctx.n = float(div), len(xc)
         return y
 
@@ -805,7 +727,7 @@ class _SumDivFn(torch.autograd.Function):
         else:
             dyc = _f32(dy)
             g = torch.empty_like(dyc)
-            check(_tl().stts_div(_ptr(dyc), dyc.numel(), ctypes.c_float(ctx.div), _ptr(g), _stream()), "stts_div")
+            check(lib().stts_div(_ptr(dyc), dyc.numel(), ctypes.c_float(ctx.div), _ptr(g), _stream()), "stts_div")
         # every input gets its own tensor: the inputs may come from concurrent branches (CONCURRENT_BRANCHES), and
         # autograd may accumulate a gradient in place on one stream while another branch's stream still reads a
         # shared one
@@ -834,16 +756,15 @@ class _SourceFn(torch.autograd.Function):
             raise ValueError(f"noise {tuple(nz.shape)}: expected {(B, L, 9)}")
         sw = torch.empty(B, L, 9, dtype=torch.float32, device=fc.device)
         har = torch.empty(B, L, dtype=torch.float32, device=fc.device)
-        nb = _tl().stts_source_workspace_bytes(B, n)
-        ws = _ws(nb, fc.device)
+        ws, nb = _workspace("stts_source_workspace_bytes", fc.device, B, n)
         if isinstance(seed, torch.Tensor):  # a device int64 [1] (the capturable step): the kernel reads it
             if not seed.is_cuda or seed.dtype != torch.int64:
                 raise TypeError("seed tensor: int64 on the device")
-            check(_tl().stts_source_fwd_seed_dev(_ptr(fc), _ptr(wc), _ptr(bc), _ptr(nz), _ptr(seed), int(utt_offset), B,
+            check(lib().stts_source_fwd_seed_dev(_ptr(fc), _ptr(wc), _ptr(bc), _ptr(nz), _ptr(seed), int(utt_offset), B,
                                                  n, int(scale), _ptr(sw), _ptr(har), _ptr(ws), int(nb), _stream()),
                   "stts_source_fwd_seed_dev")
         else:
-            check(_tl().stts_source_fwd(_ptr(fc), _ptr(wc), _ptr(bc), _ptr(nz),
+            check(lib().stts_source_fwd(_ptr(fc), _ptr(wc), _ptr(bc), _ptr(nz),
                                         ctypes.c_ulonglong(int(seed) & (2**64 - 1)), int(utt_offset), B, n, int(scale),
                                         _ptr(sw), _ptr(har), _ptr(ws), int(nb), _stream()), "stts_source_fwd")
         ctx.save_for_backward(sw, har)
@@ -861,9 +782,8 @@ class _SourceFn(torch.autograd.Function):
         d = _f32(dhar)
         dW = torch.empty(9, dtype=torch.float32, device=d.device)
         db = torch.empty(1, dtype=torch.float32, device=d.device)
-        nbytes = _tl().stts_source_workspace_bytes(B, n)
-        ws = _ws(nbytes, d.device)
-        check(_tl().stts_source_bwd(_ptr(sw), _ptr(har), _ptr(d), B, L, _ptr(dW), _ptr(db), _ptr(ws), int(nbytes),
+        ws, nbytes = _workspace("stts_source_workspace_bytes", d.device, B, n)
+        check(lib().stts_source_bwd(_ptr(sw), _ptr(har), _ptr(d), B, L, _ptr(dW), _ptr(db), _ptr(ws), int(nbytes),
                                     _stream()), "stts_source_bwd")
         return None, (dW.reshape(lw_shape) if nw else None), (db.reshape(lb_shape) if nbias else None), None, None, \
             None, None
@@ -878,7 +798,7 @@ class _BoxFn(torch.autograd.Function):
         xc = _f32(x)
         B, n = xc.shape
         y = torch.empty_like(xc)
-        check(_tl().stts_box_smooth_fwd(_ptr(xc), B, n, int(k), _ptr(y), _stream()), "stts_box_smooth_fwd")
+        check(lib().stts_box_smooth_fwd(_ptr(xc), B, n, int(k), _ptr(y), _stream()), "stts_box_smooth_fwd")
         ctx.k = int(k)
         return y
 
@@ -887,7 +807,7 @@ class _BoxFn(torch.autograd.Function):
         d = _f32(dy)
         B, n = d.shape
         dx = torch.empty_like(d)
-        check(_tl().stts_box_smooth_bwd(_ptr(d), B, n, ctx.k, _ptr(dx), _stream()), "stts_box_smooth_bwd")
+        check(lib().stts_box_smooth_bwd(_ptr(d), B, n, ctx.k, _ptr(dx), _stream()), "stts_box_smooth_bwd")
         return dx, None
 
 
@@ -919,7 +839,7 @@ class _TimeExpandFn(torch.autograd.Function):
         yc = _f32(y)
         S, H, W, C = yc.shape
         x3 = torch.empty(S, H, W, 3 * C, dtype=torch.float32, device=yc.device)
-        check(_tl().stts_time_expand3(_ptr(yc), S, H, W, C, _ptr(x3), _stream()), "stts_time_expand3")
+        check(lib().stts_time_expand3(_ptr(yc), S, H, W, C, _ptr(x3), _stream()), "stts_time_expand3")
         ctx.shape = (S, H, W, C)
         return x3
 
@@ -928,7 +848,7 @@ class _TimeExpandFn(torch.autograd.Function):
         S, H, W, C = ctx.shape
         d = _f32(dx3)
         dy = torch.empty(S, H, W, C, dtype=torch.float32, device=d.device)
-        check(_tl().stts_time_expand3_bwd(_ptr(d), S, H, W, C, _ptr(dy), _stream()), "stts_time_expand3_bwd")
+        check(lib().stts_time_expand3_bwd(_ptr(d), S, H, W, C, _ptr(dy), _stream()), "stts_time_expand3_bwd")
         return dy
 
 
@@ -959,9 +879,7 @@ class _ConvTxFn(torch.autograd.Function):
         wc = _f32(w)
         wtx = wc.permute(0, 2, 1, 3).contiguous()  # [Cout][3][C][kw]: K index dh C + c
         bc = _f32(bias) if bias is not None else None
-        nb = lib().stts_conv1d_fwd_tx_workspace_bytes(dt, S, H, W, C, co, kw, stride, pad, Lq)
-        check(int(nb) if nb < 0 else 0, "stts_conv1d_fwd_tx_workspace_bytes")
-        ws = _ws(nb, hf.device)
+        ws, nb = _workspace("stts_conv1d_fwd_tx_workspace_bytes", hf.device, dt, S, H, W, C, co, kw, stride, pad, Lq)
         y = torch.empty(S * H, Lq, co, dtype=torch.float32, device=hf.device)
         check(lib().stts_conv1d_fwd_tx(dt, _ptr(hf), _ptr(wtx), _ptr(bc), S, H, W, C, co, kw, stride, pad, Lq,
                                        int(act is not None), ctypes.c_float(act if act is not None else 0.0), _ptr(y),
@@ -988,9 +906,7 @@ class _ConvTxFn(torch.autograd.Function):
         dh = None
         if need_x and co == 32:  # d h straight from dy (no dx3 image, no fold)
             wd = wc.flip(2).permute(2, 0, 1, 3).contiguous()  # [3][Cout][C][kw]: chunk j = row dh = 2 - j
-            nb = lib().stts_conv1d_bwd_tx_workspace_bytes(dt, S, H, W, C, co, kw, stride, pad, Lq)
-            check(int(nb) if nb < 0 else 0, "stts_conv1d_bwd_tx_workspace_bytes")
-            ws = _ws(nb, dev)
+            ws, nb = _workspace("stts_conv1d_bwd_tx_workspace_bytes", dev, dt, S, H, W, C, co, kw, stride, pad, Lq)
             dh = torch.empty(S, H, W, C, dtype=torch.float32, device=dev)
             check(lib().stts_conv1d_bwd_tx(dt, _ptr(dyf), _ptr(wd), S, H, W, C, co, kw, stride, pad, Lq, _ptr(dh),
                                            _ptr(ws), int(nb), _stream()), "stts_conv1d_bwd_tx")
@@ -999,9 +915,7 @@ class _ConvTxFn(torch.autograd.Function):
         need_b = need_b and has_bias
         dx3 = dw = db = None
         if not need_x and (need_w or need_b) and dt == 1 and (kw, stride) in _WGRAD_TX:  # bf16: no x3 either
-            nb = lib().stts_conv1d_bwd_workspace_bytes(dt, B, W, Cin, co, kw, stride, 1, pad, Lq)
-            check(int(nb) if nb < 0 else 0, "stts_conv1d_bwd_workspace_bytes")
-            ws = _ws(nb, dev)
+            ws, nb = _workspace("stts_conv1d_bwd_workspace_bytes", dev, dt, B, W, Cin, co, kw, stride, 1, pad, Lq)
             dwt = torch.empty(co, 3, C, kw, dtype=torch.float32, device=dev)
             db = torch.empty(co, dtype=torch.float32, device=dev) if need_b else None
             check(lib().stts_conv1d_wgrad_tx(dt, _ptr(hf), _ptr(dyf), S, H, W, C, co, kw, stride, pad, Lq, _ptr(dwt),
@@ -1011,10 +925,8 @@ class _ConvTxFn(torch.autograd.Function):
             need_w = need_b = False
         if need_x or need_w or need_b:  # (the G step's frozen discriminators skip this: d h only)
             x3 = torch.empty(S, H, W, Cin, dtype=torch.float32, device=dev)
-            check(_tl().stts_time_expand3(_ptr(hf), S, H, W, C, _ptr(x3), _stream()), "stts_time_expand3")
-            nb = lib().stts_conv1d_bwd_workspace_bytes(dt, B, W, Cin, co, kw, stride, 1, pad, Lq)
-            check(int(nb) if nb < 0 else 0, "stts_conv1d_bwd_workspace_bytes")
-            ws = _ws(nb, dev)
+            check(lib().stts_time_expand3(_ptr(hf), S, H, W, C, _ptr(x3), _stream()), "stts_time_expand3")
+            ws, nb = _workspace("stts_conv1d_bwd_workspace_bytes", dev, dt, B, W, Cin, co, kw, stride, 1, pad, Lq)
             dx3 = torch.empty(B, W, Cin, dtype=torch.float32, device=dev) if need_x else None
             dw = torch.empty(co, Cin, kw, dtype=torch.float32, device=dev) if need_w else None
             db = torch.empty(co, dtype=torch.float32, device=dev) if need_b else None
@@ -1024,7 +936,7 @@ class _ConvTxFn(torch.autograd.Function):
             _count("bwd", 2.0 * B * Lq * co * Cin * kw * ((dx3 is not None) + (dw is not None)))
         if dx3 is not None:
             dh = torch.empty(S, H, W, C, dtype=torch.float32, device=dev)
-            check(_tl().stts_time_expand3_bwd(_ptr(dx3), S, H, W, C, _ptr(dh), _stream()), "stts_time_expand3_bwd")
+            check(lib().stts_time_expand3_bwd(_ptr(dx3), S, H, W, C, _ptr(dh), _stream()), "stts_time_expand3_bwd")
         if dw is not None and dw.dim() == 3:
             dw = dw.reshape(co, C, 3, kw)
         return dh, dw, db, None, None, None, None
@@ -1042,7 +954,7 @@ class _StftMagFn(torch.autograd.Function):
         nb = n_fft // 2 + 1
         mag = torch.empty(S, F_, nb, dtype=torch.float32, device=w.device)
         spec = torch.empty(S, F_, nb, 2, dtype=torch.float32, device=w.device)
-        check(_tl().stts_stft_mag_fwd(_ptr(w), S, L, L, n_fft, win, hop, _ptr(mag), _ptr(spec), _stream()),
+        check(lib().stts_stft_mag_fwd(_ptr(w), S, L, L, n_fft, win, hop, _ptr(mag), _ptr(spec), _stream()),
               "stts_stft_mag_fwd")
         ctx.save_for_backward(spec)
         ctx.geo = (S, L, n_fft, win, hop)
@@ -1054,10 +966,8 @@ class _StftMagFn(torch.autograd.Function):
         S, L, n_fft, win, hop = ctx.geo
         d = _f32(dmag)
         dw = torch.empty(S, L, dtype=torch.float32, device=d.device)
-        nb = _tl().stts_stft_mag_workspace_bytes(S, L, n_fft, win, hop)
-        check(int(nb) if nb < 0 else 0, "stts_stft_mag_workspace_bytes")
-        ws = _ws(nb, d.device)
-        check(_tl().stts_stft_mag_bwd(_ptr(spec), _ptr(d), S, L, n_fft, win, hop, _ptr(dw), _ptr(ws), int(nb),
+        ws, nb = _workspace("stts_stft_mag_workspace_bytes", d.device, S, L, n_fft, win, hop)
+        check(lib().stts_stft_mag_bwd(_ptr(spec), _ptr(d), S, L, n_fft, win, hop, _ptr(dw), _ptr(ws), int(nb),
                                       _stream()), "stts_stft_mag_bwd")
         return dw, None, None, None
 
@@ -1201,7 +1111,7 @@ class _DWConvFn(torch.autograd.Function):
         K = w.shape[-1]
         xc, wc, bc = _f32(x), _f32(w).reshape(C, K), (_f32(bias) if bias is not None else None)
         y = torch.empty_like(xc)
-        check(_tl().stts_dwconv1d_fwd(_ptr(xc), _ptr(wc), _ptr(bc), B, L, C, K, _ptr(y), _stream()),
+        check(lib().stts_dwconv1d_fwd(_ptr(xc), _ptr(wc), _ptr(bc), B, L, C, K, _ptr(y), _stream()),
               "stts_dwconv1d_fwd")
         ctx.save_for_backward(xc, wc)
         ctx.w_shape, ctx.has_b = w.shape, bias is not None
@@ -1217,10 +1127,8 @@ class _DWConvFn(torch.autograd.Function):
         dx = torch.empty_like(xc) if nx else None
         dw = torch.empty(C, K, dtype=torch.float32, device=dy.device) if nw else None
         db = torch.empty(C, dtype=torch.float32, device=dy.device) if (nbias and ctx.has_b) else None
-        nb = _tl().stts_dwconv1d_bwd_workspace_bytes(B, L, C, K)
-        check(int(nb) if nb < 0 else 0, "stts_dwconv1d_bwd_workspace_bytes")
-        ws = _ws(nb, dy.device)
-        check(_tl().stts_dwconv1d_bwd(_ptr(xc), _ptr(wc), _ptr(dy), B, L, C, K, _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws),
+        ws, nb = _workspace("stts_dwconv1d_bwd_workspace_bytes", dy.device, B, L, C, K)
+        check(lib().stts_dwconv1d_bwd(_ptr(xc), _ptr(wc), _ptr(dy), B, L, C, K, _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws),
                                       int(nb), _stream()), "stts_dwconv1d_bwd")
         return dx, (dw.reshape(ctx.w_shape) if dw is not None else None), db
 
@@ -1237,7 +1145,7 @@ class _GeluFn(torch.autograd.Function):
         _require_device()
         xc = _f32(x)
         y = torch.empty_like(xc)
-        check(_tl().stts_gelu_fwd(_ptr(xc), xc.numel(), _ptr(y), _stream()), "stts_gelu_fwd")
+        check(lib().stts_gelu_fwd(_ptr(xc), xc.numel(), _ptr(y), _stream()), "stts_gelu_fwd")
         ctx.save_for_backward(xc)
         return y
 
@@ -1246,7 +1154,7 @@ class _GeluFn(torch.autograd.Function):
         (xc,) = ctx.saved_tensors
         dy = _f32(gy)
         dx = torch.empty_like(xc)
-        check(_tl().stts_gelu_bwd(_ptr(xc), _ptr(dy), xc.numel(), _ptr(dx), _stream()), "stts_gelu_bwd")
+        check(lib().stts_gelu_bwd(_ptr(xc), _ptr(dy), xc.numel(), _ptr(dx), _stream()), "stts_gelu_bwd")
         return dx
 
 
@@ -1265,7 +1173,7 @@ class _LayerScaleResFn(torch.autograd.Function):
         if rc.shape != xc.shape or gc.numel() != C:
             raise ValueError(f"layer scale: x {tuple(x.shape)}, r {tuple(r.shape)}, gamma {tuple(gamma.shape)}")
         y = torch.empty_like(xc)
-        check(_tl().stts_layer_scale_res_fwd(_ptr(xc), _ptr(rc), _ptr(gc), B, L, C, _ptr(y), _stream()),
+        check(lib().stts_layer_scale_res_fwd(_ptr(xc), _ptr(rc), _ptr(gc), B, L, C, _ptr(y), _stream()),
               "stts_layer_scale_res_fwd")
         ctx.save_for_backward(xc, gc)
         ctx.g_shape = gamma.shape
@@ -1279,10 +1187,8 @@ class _LayerScaleResFn(torch.autograd.Function):
         nx, nr, ng = ctx.needs_input_grad
         dx = torch.empty_like(xc) if nx else None
         dg = torch.empty(C, dtype=torch.float32, device=dy.device) if ng else None
-        nb = _tl().stts_layer_scale_res_bwd_workspace_bytes(B, L, C)
-        check(int(nb) if nb < 0 else 0, "stts_layer_scale_res_bwd_workspace_bytes")
-        ws = _ws(nb, dy.device)
-        check(_tl().stts_layer_scale_res_bwd(_ptr(xc), _ptr(gc), _ptr(dy), B, L, C, _ptr(dx), _ptr(dg), _ptr(ws),
+        ws, nb = _workspace("stts_layer_scale_res_bwd_workspace_bytes", dy.device, B, L, C)
+        check(lib().stts_layer_scale_res_bwd(_ptr(xc), _ptr(gc), _ptr(dy), B, L, C, _ptr(dx), _ptr(dg), _ptr(ws),
                                              int(nb), _stream()), "stts_layer_scale_res_bwd")
         return dx, (gy if nr else None), (dg.reshape(ctx.g_shape) if dg is not None else None)
 
@@ -1302,11 +1208,9 @@ class _ISTFTHeadFn(torch.autograd.Function):
         if W != n_fft + 2 or window.numel() != n_fft:
             raise ValueError(f"ISTFT head: h {tuple(h.shape)}, window {tuple(window.shape)} for n_fft {n_fft}")
         hc, wc = _f32(h), _f32(window)
-        nb = _tl().stts_istft_head_workspace_bytes(B, F, n_fft, hop)
-        check(int(nb) if nb < 0 else 0, "stts_istft_head_workspace_bytes")
-        ws = _ws(nb, h.device)
+        ws, nb = _workspace("stts_istft_head_workspace_bytes", h.device, B, F, n_fft, hop)
         y = torch.empty(B, F * hop, dtype=torch.float32, device=h.device)
-        check(_tl().stts_istft_head_fwd(_ptr(hc), _ptr(wc), B, F, n_fft, hop, _ptr(y), _ptr(ws), int(nb), _stream()),
+        check(lib().stts_istft_head_fwd(_ptr(hc), _ptr(wc), B, F, n_fft, hop, _ptr(y), _ptr(ws), int(nb), _stream()),
               "stts_istft_head_fwd")
         ctx.save_for_backward(hc, wc)
         ctx.geo = (n_fft, hop)
@@ -1319,7 +1223,7 @@ class _ISTFTHeadFn(torch.autograd.Function):
         B, F, _ = hc.shape
         dy = _f32(gy)
         dh = torch.empty_like(hc)
-        check(_tl().stts_istft_head_bwd(_ptr(hc), _ptr(wc), _ptr(dy), B, F, n_fft, hop, _ptr(dh), None, 0, _stream()),
+        check(lib().stts_istft_head_bwd(_ptr(hc), _ptr(wc), _ptr(dy), B, F, n_fft, hop, _ptr(dh), None, 0, _stream()),
               "stts_istft_head_bwd")
         return dh, None, None, None
 
@@ -1388,7 +1292,7 @@ class _CSTFTFn(torch.autograd.Function):
         if wr.numel() != nb * n_fft or wi.numel() != nb * n_fft:
             raise ValueError(f"CustomSTFT: forward bases {tuple(wr.shape)} / {tuple(wi.shape)} for n_fft {n_fft}")
         out = torch.empty(B, L // hop + 1, n_fft + 2, dtype=torch.float32, device=w.device)
-        check(_tl().stts_cstft_fwd(_ptr(w), _ptr(_f32(wr)), _ptr(_f32(wi)), B, L, n_fft, hop, _ptr(out), _stream()),
+        check(lib().stts_cstft_fwd(_ptr(w), _ptr(_f32(wr)), _ptr(_f32(wi)), B, L, n_fft, hop, _ptr(out), _stream()),
               "stts_cstft_fwd")
         ctx.mark_non_differentiable(out)
         return out
@@ -1413,7 +1317,7 @@ class _PadLAddFn(torch.autograd.Function):
             raise ValueError(f"padl_add: x {tuple(x.shape)}, src {tuple(src.shape)}: expected {(B, L + 1, C)}")
         xc, sc = _f32(x), _f32(src)
         y = torch.empty_like(sc)
-        check(_tl().stts_padl_add_fwd(_ptr(xc), _ptr(sc), B, L, C, _ptr(y), _stream()), "stts_padl_add_fwd")
+        check(lib().stts_padl_add_fwd(_ptr(xc), _ptr(sc), B, L, C, _ptr(y), _stream()), "stts_padl_add_fwd")
         ctx.shape = (B, L, C)
         return y
 
@@ -1425,7 +1329,7 @@ class _PadLAddFn(torch.autograd.Function):
         if nx:
             dy = _f32(gy)
             dx = torch.empty(B, L, C, dtype=torch.float32, device=dy.device)
-            check(_tl().stts_padl_add_bwd(_ptr(dy), B, L, C, _ptr(dx), _stream()), "stts_padl_add_bwd")
+            check(lib().stts_padl_add_bwd(_ptr(dy), B, L, C, _ptr(dx), _stream()), "stts_padl_add_bwd")
         return dx, (gy if ns else None)  # dx is its own tensor (see _SumDivFn.backward); src's gradient is dy itself
 
 
@@ -1447,7 +1351,7 @@ class _CISTFTHeadFn(torch.autograd.Function):
                              f"for n_fft {n_fft}")
         pc, brc, bic = _f32(post), _f32(br), _f32(bi)
         y = torch.empty(B, max(F - 1, 0) * hop, dtype=torch.float32, device=pc.device)
-        check(_tl().stts_cistft_head_fwd(_ptr(pc), _ptr(brc), _ptr(bic), B, F, n_fft, hop, _ptr(y), _stream()),
+        check(lib().stts_cistft_head_fwd(_ptr(pc), _ptr(brc), _ptr(bic), B, F, n_fft, hop, _ptr(y), _stream()),
               "stts_cistft_head_fwd")
         ctx.save_for_backward(pc, brc, bic)
         ctx.geo = (n_fft, hop)
@@ -1460,7 +1364,7 @@ class _CISTFTHeadFn(torch.autograd.Function):
         B, F, _ = pc.shape
         dy = _f32(gy)
         dp = torch.empty_like(pc)
-        check(_tl().stts_cistft_head_bwd(_ptr(pc), _ptr(brc), _ptr(bic), _ptr(dy), B, F, n_fft, hop, _ptr(dp),
+        check(lib().stts_cistft_head_bwd(_ptr(pc), _ptr(brc), _ptr(bic), _ptr(dy), B, F, n_fft, hop, _ptr(dp),
                                          _stream()), "stts_cistft_head_bwd")
         return dp, None, None, None, None
 
@@ -1610,7 +1514,7 @@ class _DropoutFn(torch.autograd.Function):
         xc = _c(x)
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         y = torch.empty_like(xc)
-        check(_tl().stts_dropout(_ptr(xc), xc.numel(), ctypes.c_float(p), ctypes.c_ulonglong(seed), _ptr(y),
+        check(lib().stts_dropout(_ptr(xc), xc.numel(), ctypes.c_float(p), ctypes.c_ulonglong(seed), _ptr(y),
                                  _stream()), "stts_dropout")
         ctx.p, ctx.seed = p, seed
         return y
@@ -1619,7 +1523,7 @@ class _DropoutFn(torch.autograd.Function):
     def backward(ctx, dy):
         dyc = _c(dy)
         dx = torch.empty_like(dyc)
-        check(_tl().stts_dropout(_ptr(dyc), dyc.numel(), ctypes.c_float(ctx.p), ctypes.c_ulonglong(ctx.seed),
+        check(lib().stts_dropout(_ptr(dyc), dyc.numel(), ctypes.c_float(ctx.p), ctypes.c_ulonglong(ctx.seed),
                                  _ptr(dx), _stream()), "stts_dropout")
         return dx, None
 
@@ -1634,7 +1538,7 @@ class _DropoutMaskFn(torch.autograd.Function):
         if mc.shape != xc.shape:
             raise ValueError(f"dropout mask {tuple(mc.shape)} for a tensor {tuple(xc.shape)}")
         y = torch.empty_like(xc)
-        check(_tl().stts_dropout_mask(_ptr(xc), _ptr(mc), xc.numel(), ctypes.c_float(p), _ptr(y), _stream()),
+        check(lib().stts_dropout_mask(_ptr(xc), _ptr(mc), xc.numel(), ctypes.c_float(p), _ptr(y), _stream()),
               "stts_dropout_mask")
         ctx.save_for_backward(mc)
         ctx.p = p
@@ -1645,7 +1549,7 @@ class _DropoutMaskFn(torch.autograd.Function):
         (mc,) = ctx.saved_tensors
         dyc = _c(dy)
         dx = torch.empty_like(dyc)
-        check(_tl().stts_dropout_mask(_ptr(dyc), _ptr(mc), dyc.numel(), ctypes.c_float(ctx.p), _ptr(dx), _stream()),
+        check(lib().stts_dropout_mask(_ptr(dyc), _ptr(mc), dyc.numel(), ctypes.c_float(ctx.p), _ptr(dx), _stream()),
               "stts_dropout_mask")
         return dx, None, None
 
@@ -1691,9 +1595,8 @@ class _BiLSTMFn(torch.autograd.Function):
         ps = [_c(p) for p in params]
         H = ps[1].shape[1]
         arr = (ctypes.c_void_p * 8)(*[p.data_ptr() for p in ps])
-        L = _tl()
-        nb = int(L.stts_bilstm_workspace_bytes(B, T, H))
-        ws = _ws(nb, x.device)
+        L = lib()
+        ws, nb = _workspace("stts_bilstm_workspace_bytes", x.device, B, T, H)
         y = torch.empty(B, T, 2 * H, dtype=torch.float32, device=x.device)
         cs = torch.empty(2, B, T, H, dtype=torch.float32, device=x.device)
         check(L.stts_bilstm_fwd_train(_ptr(xc), T * Cin, Cin, 1, B, T, Cin, _ptr(ln), arr, H, _ptr(y), _ptr(cs),
@@ -1714,10 +1617,8 @@ class _BiLSTMFn(torch.autograd.Function):
         grads = [torch.empty_like(p) if need[i + 2] else None for i, p in enumerate(ps)]
         arr = (ctypes.c_void_p * 8)(*[p.data_ptr() for p in ps])
         garr = (ctypes.c_void_p * 8)(*[g.data_ptr() if g is not None else None for g in grads])
-        L = _tl()
-        nb = int(L.stts_bilstm_bwd_workspace_bytes(B, T, Cin, H))
-        check(nb if nb < 0 else 0, "stts_bilstm_bwd_workspace_bytes")
-        ws = _ws(nb, dy.device)
+        L = lib()
+        ws, nb = _workspace("stts_bilstm_bwd_workspace_bytes", dy.device, B, T, Cin, H)
         check(L.stts_bilstm_bwd(_ptr(xc), B, T, Cin, _ptr(ln), arr, H, _ptr(y), _ptr(cs), _ptr(dyc), _ptr(dx), garr,
                                 _ptr(ws), nb, _stream()), "stts_bilstm_bwd")
         return (dx, None, *grads)
@@ -1756,7 +1657,7 @@ class _RowExpFn(torch.autograd.Function):
         B, H, W, C = xc.shape
         Ho = H + 2 * pad - k + 1
         xe = torch.empty(B, Ho, W, C * k, dtype=torch.float32, device=x.device)
-        check(_tl().stts_rowexp_fwd(_ptr(xc), B, H, W, C, k, pad, _ptr(xe), _stream()), "stts_rowexp_fwd")
+        check(lib().stts_rowexp_fwd(_ptr(xc), B, H, W, C, k, pad, _ptr(xe), _stream()), "stts_rowexp_fwd")
         ctx.geom = (B, H, W, C, k, pad)
         return xe
 
@@ -1765,7 +1666,7 @@ class _RowExpFn(torch.autograd.Function):
         B, H, W, C, k, pad = ctx.geom
         d = _c(dxe)
         dx = torch.empty(B, H, W, C, dtype=torch.float32, device=d.device)
-        check(_tl().stts_rowexp_bwd(_ptr(d), B, H, W, C, k, pad, _ptr(dx), _stream()), "stts_rowexp_bwd")
+        check(lib().stts_rowexp_bwd(_ptr(d), B, H, W, C, k, pad, _ptr(dx), _stream()), "stts_rowexp_bwd")
         return dx, None, None
 
 
@@ -1778,7 +1679,7 @@ class _DWConvS2Fn(torch.autograd.Function):
         xc, wc, bc = _c(x), _c(w), _c(b)
         B, H, W, C = xc.shape
         y = torch.empty(B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C, dtype=torch.float32, device=x.device)
-        check(_tl().stts_dwconv2d_s2_fwd(_ptr(xc), _ptr(wc), _ptr(bc), B, H, W, C, _ptr(y), _stream()),
+        check(lib().stts_dwconv2d_s2_fwd(_ptr(xc), _ptr(wc), _ptr(bc), B, H, W, C, _ptr(y), _stream()),
               "stts_dwconv2d_s2_fwd")
         ctx.save_for_backward(xc, wc)
         ctx.has_b = b is not None
@@ -1793,9 +1694,8 @@ class _DWConvS2Fn(torch.autograd.Function):
         dx = torch.empty_like(xc) if nx else None
         dw = torch.empty_like(wc) if nw else None
         db = torch.empty(C, dtype=torch.float32, device=d.device) if (nb_ and ctx.has_b) else None
-        L = _tl()
-        nb = int(L.stts_dwconv2d_s2_workspace_bytes(C))
-        ws = _ws(nb, d.device)
+        L = lib()
+        ws, nb = _workspace("stts_dwconv2d_s2_workspace_bytes", d.device, C)
         check(L.stts_dwconv2d_s2_bwd(_ptr(xc), _ptr(wc), _ptr(d), B, H, W, C, _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws), nb,
                                      _stream()), "stts_dwconv2d_s2_bwd")
         return dx, dw, db
@@ -1810,7 +1710,7 @@ class _AvgPool2Fn(torch.autograd.Function):
         xc = _c(x)
         B, H, W, C = xc.shape
         y = torch.empty(B, H // 2, (W + 1) // 2, C, dtype=torch.float32, device=x.device)
-        check(_tl().stts_avgpool2_fwd(_ptr(xc), B, H, W, C, _ptr(y), _stream()), "stts_avgpool2_fwd")
+        check(lib().stts_avgpool2_fwd(_ptr(xc), B, H, W, C, _ptr(y), _stream()), "stts_avgpool2_fwd")
         ctx.geom = (B, H, W, C)
         return y
 
@@ -1819,7 +1719,7 @@ class _AvgPool2Fn(torch.autograd.Function):
         B, H, W, C = ctx.geom
         d = _c(dy)
         dx = torch.empty(B, H, W, C, dtype=torch.float32, device=d.device)
-        check(_tl().stts_avgpool2_bwd(_ptr(d), B, H, W, C, _ptr(dx), _stream()), "stts_avgpool2_bwd")
+        check(lib().stts_avgpool2_bwd(_ptr(d), B, H, W, C, _ptr(dx), _stream()), "stts_avgpool2_bwd")
         return dx
 
 
@@ -1832,7 +1732,7 @@ class _SpatialMeanFn(torch.autograd.Function):
         xc = _c(x)
         B, H, W, C = xc.shape
         y = torch.empty(B, C, dtype=torch.float32, device=x.device)
-        check(_tl().stts_spatial_mean_fwd(_ptr(xc), B, H * W, C, _ptr(y), _stream()), "stts_spatial_mean_fwd")
+        check(lib().stts_spatial_mean_fwd(_ptr(xc), B, H * W, C, _ptr(y), _stream()), "stts_spatial_mean_fwd")
         ctx.geom = (B, H, W, C)
         return y
 
@@ -1841,7 +1741,7 @@ class _SpatialMeanFn(torch.autograd.Function):
         B, H, W, C = ctx.geom
         d = _c(dy)
         dx = torch.empty(B, H, W, C, dtype=torch.float32, device=d.device)
-        check(_tl().stts_spatial_mean_bwd(_ptr(d), B, H * W, C, _ptr(dx), _stream()), "stts_spatial_mean_bwd")
+        check(lib().stts_spatial_mean_bwd(_ptr(d), B, H * W, C, _ptr(dx), _stream()), "stts_spatial_mean_bwd")
         return dx
 
 

@@ -141,10 +141,10 @@ def test_frames_gemm_split_k(B, T, Cin, N, K):
     for elems in (16 * B * T * N, 2 * B * T * N, 0):
         y = torch.empty(B, T, N, device="cuda")
         ws = torch.empty(max(elems, 1), device="cuda")
-        P.check(P._L().stts_frames_gemm_ws(P._ptr(xd), *xd.stride(), B, T, Cin, P._ptr(wd), 0, wd.stride(0),
-                                           wd.stride(1), wd.stride(2), N, K, (K - 1) // 2, P._ptr(bd), None,
-                                           P._ptr(y), *y.stride(), T, P._ptr(ws) if elems else None, elems * 4,
-                                           P._stream()))
+        P.check(P.lib().stts_frames_gemm_ws(P._ptr(xd), *xd.stride(), B, T, Cin, P._ptr(wd), 0, wd.stride(0),
+                                            wd.stride(1), wd.stride(2), N, K, (K - 1) // 2, P._ptr(bd), None,
+                                            P._ptr(y), *y.stride(), T, P._ptr(ws) if elems else None, elems * 4,
+                                            P._stream()))
         outs.append(y.cpu())
     for o in outs:
         assert _err(o, want.numpy()) < 1e-4

@@ -9,7 +9,6 @@ computed in the test on the same formula weights, inputs and noise:
 
 Tolerances: fp32 max-abs <= 1e-3 (north star); bf16 correlation >= 0.99 with the fp32 oracle.
 """
-import ctypes
 
 import numpy as np
 import pytest
@@ -157,9 +156,6 @@ def _fxsum(parts, mode):
     lane with integer atomics, then read back once)."""
     from stts2_mi355x import engine as E
     L = E.lib()
-    L.stts_test_fxsum.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
-                                  ctypes.c_void_p]
-    L.stts_test_fxsum.restype = ctypes.c_int
     t = torch.as_tensor(parts, dtype=torch.float32 if mode == 0 else torch.float64).cuda()
     entry = torch.zeros(4, dtype=torch.float64, device="cuda")
     out = torch.zeros(1, dtype=torch.float64, device="cuda")

@@ -23,11 +23,6 @@ CASES = [(4, 2), (7, 1)]  # (T, B)
 _ZERO_GRAD = re.compile(r"(\.convs1\.\d+\.bias|^encode\.conv1\.bias|^decode\.\d+\.conv1\.bias)$")
 
 
-def _lib():
-    from stts2_mi355x.training import _tl
-    return _tl()
-
-
 def test_library_exports_entries():
     L = E.lib()
     for name in ENTRIES:
@@ -38,7 +33,7 @@ def test_library_exports_entries():
 def test_entries_validate_before_launch():
     """Bad geometries are refused on the host with null pointers and without a device; so are null pointers with
     a good geometry."""
-    L = _lib()
+    L = E.lib()
     p = 4096  # never dereferenced: every call below fails validation first
     # (n_fft, hop): odd n_fft, n_fft 66, n_fft 2, hop 0, hop > n_fft
     for n_fft, hop in ((21, 5), (66, 5), (2, 1), (20, 0), (20, 21)):

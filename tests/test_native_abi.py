@@ -1,5 +1,6 @@
-"""CPU tests of the C-ABI library: it loads, exports every symbol include/*.h declares,
-and its model plans name exactly the reference state-dict keys (no GPU compute here)."""
+"""CPU tests of the C-ABI library: it loads, exports every symbol include/*.h declares, the ctypes
+signature table (stts2_mi355x/abi.py) and engine's constants agree with those headers, and its model
+plans name exactly the reference state-dict keys (no GPU compute here)."""
 import ctypes
 import glob
 import os
@@ -22,12 +23,129 @@ def declared_symbols():
     return sorted(out)
 
 
+def _headers():
+    """{header name: its text with the comments stripped}."""
+    return {os.path.basename(h): re.sub(r"/\*.*?\*/", "", open(h).read(), flags=re.S)
+            for h in sorted(glob.glob(os.path.join(ROOT, "include", "*.h")))}
+
+
+# the classes a C parameter or return type reduces to; anything with a '*' is a pointer
+_C_SCALARS = {"int": "int", "long long": "long long", "unsigned long long": "unsigned long long", "float": "float",
+              "double": "double"}
+
+
+def _c_class(decl, what, is_param):
+    """Class of one C declaration (`const float* x`, `long long ws_bytes`, a bare return type): raises on anything
+    that is not a pointer, one of _C_SCALARS or a void return, so that no prototype goes by unchecked."""
+    words = decl.replace("*", " * ").split()
+    if "*" in words:
+        return "pointer"
+    words = [w for w in words if w != "const"]
+    for n in (3, 2, 1):  # the longest type name first: `unsigned long long`, then `long long`, then `int`
+        t = " ".join(words[:n])
+        if t in _C_SCALARS and len(words) == n + (1 if is_param else 0):  # a parameter carries its name
+            return _C_SCALARS[t]
+    if not is_param and words == ["void"]:
+        return "void"
+    raise AssertionError(f"{what}: cannot classify {decl!r}")
+
+
+def header_prototypes():
+    """{name: ([argument classes], return class)} of every `<type> stts_name(<params>);` in include/*.h."""
+    protos = {}
+    for fname, src in _headers().items():
+        src = re.sub(r"^\s*#.*$", "", src, flags=re.M)  # preprocessor lines
+        for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(stts_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+            assert name not in protos, f"{fname}: {name} declared twice"
+            params = params.strip()
+            args = [] if params in ("", "void") else [
+                _c_class(p, f"{fname}: {name} parameter {k}", True) for k, p in enumerate(params.split(","))]
+            protos[name] = (args, _c_class(ret, f"{fname}: {name} return type", False))
+    return protos
+
+
+def _ctypes_class(t, what):
+    """Class of one entry of abi.SIGNATURES, in header_prototypes()' terms."""
+    scalars = {ctypes.c_int: "int", ctypes.c_longlong: "long long", ctypes.c_ulonglong: "unsigned long long",
+               ctypes.c_float: "float", ctypes.c_double: "double", None: "void"}
+    if t in scalars:
+        return scalars[t]
+    if t in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(t, type) and issubclass(t, ctypes._Pointer)):
+        return "pointer"
+    raise AssertionError(f"{what}: cannot classify {t!r}")
+
+
 def test_library_exports_all_declared_symbols():
     L = E.lib()
     syms = declared_symbols()
     assert len(syms) >= 14 + 20  # stts2.h + stts2_train.h
     for s in syms:
         assert hasattr(L, s), f"libstts2.so does not export {s}"
+
+
+def test_every_prototype_is_parsed():
+    """The prototype parser sees every declared name (a prototype its regex misses is an error, not an omission)."""
+    protos = header_prototypes()
+    assert sorted(protos) == declared_symbols()
+    assert len(protos) == len(declared_symbols())
+
+
+def test_signature_table_names_the_declared_entry_points():
+    assert set(E.SIGNATURES) - set(declared_symbols()) == set(), "bound but not declared in include/*.h"
+    assert set(declared_symbols()) - set(E.SIGNATURES) == set(), "declared in include/*.h but not in abi.SIGNATURES"
+
+
+def test_signature_table_matches_the_headers():
+    """Argument count, the class of every argument and of the return value, header against abi.SIGNATURES."""
+    protos = header_prototypes()
+    bad = []
+    for name, (args, res) in E.SIGNATURES.items():
+        want_args, want_res = protos[name]
+        got_args = [_ctypes_class(t, f"{name} argument {k}") for k, t in enumerate(args)]
+        got_res = _ctypes_class(res, f"{name} restype")
+        if got_args != want_args or got_res != want_res:
+            bad.append(f"{name}: header ({', '.join(want_args)}) -> {want_res}; "
+                       f"table ({', '.join(got_args)}) -> {got_res}")
+    assert not bad, "\n".join(bad)
+
+
+def test_loaded_library_carries_the_table():
+    """After lib() every entry point of the table is typed on the loaded library, whichever module asks for it."""
+    L = E.lib()
+    for name, (args, res) in E.SIGNATURES.items():
+        fn = getattr(L, name)
+        assert fn.argtypes is not None and list(fn.argtypes) == list(args), name
+        assert fn.restype is res, name
+
+
+def _defines(prefix):
+    """{NAME: int value} of every `#define <prefix>NAME <integer>` in include/*.h."""
+    out = {}
+    for src in _headers().values():
+        for name, val in re.findall(rf"^\s*#\s*define\s+{prefix}(\w+)\s+\(?(-?\d+)\)?\s*$", src, flags=re.M):
+            assert name not in out, f"{prefix}{name} defined twice"
+            out[name] = int(val)
+    return out
+
+
+def test_constants_match_the_header():
+    """engine's ABI_VERSION, OPT_* (with a default each) and KIND_* are the header's #defines, in both directions."""
+    assert _defines("STTS_ABI_")["VERSION"] == E.ABI_VERSION
+    opts = _defines("STTS_OPT_")
+    assert opts
+    for name, val in opts.items():
+        assert getattr(E, "OPT_" + name, None) == val, f"STTS_OPT_{name} = {val}"
+        assert val in E.OPT_DEFAULTS, f"OPT_{name} has no entry in OPT_DEFAULTS"
+    for name in dir(E):
+        if name.startswith("OPT_") and name != "OPT_DEFAULTS":
+            assert name[4:] in opts, f"engine.{name} has no #define STTS_{name}"
+    kinds = _defines("STTS_KIND_")
+    assert kinds
+    for name, val in kinds.items():
+        assert getattr(E, "KIND_" + name, None) == val, f"STTS_KIND_{name} = {val}"
+    for name in dir(E):
+        if name.startswith("KIND_"):
+            assert name[5:] in kinds, f"engine.{name} has no #define STTS_{name}"
 
 
 def _plan(kind, cfg):
@@ -122,8 +240,7 @@ def test_style_plan_names_match_state_dict():
 
 def test_duration_path_argument_checks():
     """The duration-path entry points validate shapes before touching the device (include/stts2.h)."""
-    from stts2_mi355x import prosody
-    L = prosody._L()
+    L = E.lib()
     assert L.stts_bilstm_workspace_bytes(2, 10, 256) == ((2 * 2 * 10 * 1024 + 2 * 256 * 1024) * 4 + 2 * 2 * 2 * 256 * 8 + 8
                                                           + 16 * 2 * 10 * 1024 * 4)  # split-K scratch (B T <= 256)
     assert L.stts_bilstm_workspace_bytes(32, 400, 256) == (2 * 32 * 400 * 1024 + 2 * 256 * 1024) * 4 + 2 * 32 * 2 * 256 * 8 + 8
@@ -176,8 +293,7 @@ def test_retired_option_keys_are_invalid(key):
 
 def test_bilstm_error_word_offset():
     """The BiLSTM error word lies inside the workspace, 8-byte aligned, before the exchange words."""
-    from stts2_mi355x import prosody
-    L = prosody._L()
+    L = E.lib()
     for B, T, H in ((1, 5, 256), (4, 37, 256), (32, 400, 256), (3, 7, 64)):
         off = L.stts_bilstm_error_offset(B, T, H)
         assert 0 < off and off % 8 == 0 and off + 8 <= L.stts_bilstm_workspace_bytes(B, T, H)

@@ -45,11 +45,6 @@ def head_masks(h, n_fft):
     return e > CLIP, (e - CLIP).abs() <= NEAR * CLIP
 
 
-def _lib():
-    from stts2_mi355x.training import _tl
-    return _tl()
-
-
 def _al(n):
     return (n + 255) & ~255
 
@@ -62,7 +57,7 @@ def test_library_exports_entries_and_queries():
 
 
 def test_workspace_queries():
-    L = _lib()
+    L = E.lib()
     dw = L.stts_dwconv1d_bwd_workspace_bytes
     assert dw(2, 77, 512, 7) == _al(2 * 3 * 512 * 8 * 8)          # S = ceil(77 / 32) = 3
     assert dw(1, 100000, 100, 3) == _al(1 * 64 * 100 * 4 * 8)     # S capped at 64; C no multiple of 256
@@ -87,7 +82,7 @@ def test_workspace_queries():
 
 def test_entries_validate_before_launch():
     """Null or short arguments are refused on the host: these calls run without a device."""
-    L = _lib()
+    L = E.lib()
     p = 4096  # never dereferenced: every call below fails validation first
     assert L.stts_dwconv1d_fwd(None, p, p, 2, 77, 512, 7, p, None) == EINVAL
     assert L.stts_dwconv1d_fwd(p, None, p, 2, 77, 512, 7, p, None) == EINVAL

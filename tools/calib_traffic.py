@@ -11,7 +11,6 @@ moves, i.e. the factor that turns the counter into bytes for that pattern.
 """
 import argparse
 import csv
-import ctypes
 import glob
 import json
 import os
@@ -38,8 +37,6 @@ def run(a):
     import torch
     from stts2_mi355x import engine as E
     L = E.lib()
-    L.stts_calib_traffic.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int,
-                                     ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     buf = torch.zeros(a.rows * a.ld, dtype=torch.bfloat16, device="cuda")
     scrub = torch.empty(64 * 1024 * 1024, dtype=torch.float32, device="cuda")
     grid = 1024

@@ -9,7 +9,6 @@ from stts2_mi355x import engine as E  # noqa: E402
 from stts2_mi355x.training import out_length  # noqa: E402
 
 L = E.lib()
-L.stts_test_conv1d.restype = ctypes.c_int
 for (B, Cin, Cout, K, s, d, p, Lin) in [(2, 1090, 1024, 3, 1, 1, 1, 40), (2, 1090, 512, 3, 1, 1, 1, 40),
                                         (2, 1, 1, 3, 2, 1, 1, 80), (2, 16, 1, 3, 2, 1, 1, 80)]:
     Lq = out_length(Lin, K, s, p, d)
