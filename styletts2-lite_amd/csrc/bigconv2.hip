@@ -840,9 +840,6 @@ int launch_b2_c(const ConvParams& p, hipStream_t s) {
 
 // STTS_OPT_BIGCONV: 1 = bigconv.hip (v1, A/B); 2 = this engine, 8-wave blocks (one per CU);
 // 3 = this engine, 4-wave blocks (two per CU, C = 256 split into two 128-channel output parts)
-int g_opt_bigconv = 2;
-// STTS_OPT_EXP: the reference layouts of three bitwise tests (bits 32 / 64 here, 32768 in resconv.hip)
-int g_opt_exp = 0;
 
 bool st_bigconv2_eligible(const ConvParams& p) {
   if (g_opt_bigconv < 2) return false;
@@ -866,7 +863,6 @@ static int b2_num_cu() {
 // ---- decoder front-end (AdainResBlk1d k3 convs, hifigan.py:359-403 / 427-432): C_out 1024 / 512
 // in 256-channel output parts, C_in up to 1120 (the 1090-channel concat), [AdaIN ->] LReLU prologue
 constexpr int FE_CINP = 1120;
-int g_opt_front = 1;
 
 bool st_front_eligible(const ConvParams& p, int dtype) {
   if (!g_opt_front || dtype != ST_BF16) return false;
@@ -917,7 +913,6 @@ int st_bigconv2(const ConvParams& p, hipStream_t stream) {
 // ---- the wide polyphase upsamplers (HiFi-GAN ups[0] 512 -> 256 x10, N = 2,560; ups[1] 256 -> 128 x5,
 // N = 640; hifigan.py:292-294 with the Snake(alphas[i]) prologue of :333 and the noise-branch residual
 // x + x_source of :335): 2 taps, on this engine instead of conv1d_igemm (STTS_OPT_UPS, default on)
-int g_opt_ups = 1;
 
 bool st_ups_eligible(const ConvParams& p, int dtype) {
   if (!g_opt_ups || dtype != ST_BF16 || p.up <= 1 || !p.res || p.accb) return false;
@@ -949,7 +944,6 @@ int st_bigconv2_ups(const ConvParams& p, hipStream_t s) {
 // wave slices (NF = 4): 4-wave blocks (two per CU) of 2 frame slices x 2 output blocks, 256-frame tiles (bit 4; else
 // 8-wave blocks, 512-frame tiles).  STTS_OPT_BIG64 bit 1:
 // the accuracy mode's (replacing the two-pass split resblock engine), bit 2: bf16 (replacing resconv)
-int g_opt_big64 = 5;  // (SP on 4-wave blocks: 2-7 % faster per launch than 8-wave, profiles/r05_ab_big64.txt)
 
 bool st_big64_eligible(const ConvParams& p, int dtype) {
   const int C = p.Cout;
@@ -983,7 +977,6 @@ int st_big64(const ConvParams& p, int dtype, hipStream_t s) {
 // ---- the split-operand accuracy mode (STTS_SPLIT, dtype ST_SPLIT: fp32 frames, bf16 hi + lo operands) on this
 // engine (SP): the C = 128 / 256 resblock convs, the front-end k3 convs and ups[0] / ups[1], which ran on the split
 // conv1d_igemm (STTS_OPT_BIGSPLIT, default on; 0 = the split igemm, A/B)
-int g_opt_bigsplit = 1;
 
 bool st_bigsplit_eligible(const ConvParams& p, int dtype) {
   if (!g_opt_bigsplit || dtype != ST_SPLIT) return false;

@@ -902,11 +902,6 @@ int launch_typed(const ConvParams& p, hipStream_t stream) {
 
 }  // namespace
 
-int g_opt_resconv = 1;
-int g_opt_small_tiles = 1;
-int g_opt_grid_cap = 0;
-int g_opt_segpart = 1;
-
 // (only launches that keep InstanceNorm statistics: a conv's outputs do not depend on the tile -> workgroup split, its
 // statistics' fp32 partials do.  A plain launch over many short rows — the discriminators' reshaped batches — would
 // otherwise get mostly empty segments, each re-staging the layer's weights: 2.3x slower igemm in the training step)
@@ -916,8 +911,7 @@ int st_seg_choice(const ConvParams& p, int upu, int gmax) {
   const int seg = gmax / (32 * upu);
   return seg >= 1 ? seg : 0;
 }
-int g_opt_debug = 0;
-int g_opt_head = 1;
+
 unsigned long long* g_dbg_stamps = nullptr;  // stts_set_debug_buffer
 
 int st_conv1d_engine(const ConvParams& p, int dtype) {

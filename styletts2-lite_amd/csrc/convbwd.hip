@@ -23,11 +23,6 @@
 #include "common.h"
 #include "kernels.h"
 
-int g_opt_bf16f = 0;  // STTS_OPT_BF16F: bf16 training convs on the general engine read / write fp32 frames
-int g_opt_yf32 = 1;   // STTS_OPT_YF32: ... store fp32 output frames from the accumulators
-int g_opt_cout1 = 1;  // STTS_OPT_COUT1: one-output-channel forwards as a GEMV (k_conv_cout1)
-int g_opt_wgw = 1;  // k_wgrad_bf16w for the stride-1 convs (STTS_OPT_WGRAD); 0 = the per-tap kernel everywhere
-
 namespace {
 
 constexpr int kTargetWaves = 2048;  // 8 waves per CU on 256 CUs

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "common.h"
+#include "options.h"  // the g_opt_* engine options (STTS_OPT_*)
 
 // ---------------------------------------------------------------- conv1d_igemm
 struct ConvParams {
@@ -91,7 +92,6 @@ __device__ __forceinline__ void tile_range(const ConvParams& p, int v, int nv, l
 // Segmented when B is a multiple of 32 (every config-4 shard, 256 / W utterances): seg = gmax / (32 upu), so B = 32 k
 // gives every workgroup k ranges of equal size; 0 (the even split) otherwise, or with STTS_OPT_SEGPART 0
 int st_seg_choice(const ConvParams& p, int upu, int gmax);
-extern int g_opt_segpart;
 
 int st_conv1d(const ConvParams& p, int dtype, hipStream_t stream);
 // slot base of workgroup `g` (see ConvParams::stats_slots)
@@ -109,29 +109,20 @@ enum { ST_ENGINE_IGEMM = 0, ST_ENGINE_RESCONV = 1, ST_ENGINE_BIGCONV = 2, ST_ENG
 // split-operand (ST_SPLIT) resblock convs, C = 32 / 64 (ressplit.hip; C = 64 needs p.splitk_ws >= B Lq 64 floats)
 bool st_ressplit_eligible(const ConvParams& p, int dtype);
 int st_ressplit(const ConvParams& p, hipStream_t stream);
-extern int g_opt_ressplit;
 // split-operand (ST_SPLIT) C = 128 / 256 resblock convs, front-end k3 convs, ups[0] / ups[1] on the bigconv2
 // engine (bigconv2.hip, SP)
 bool st_bigsplit_eligible(const ConvParams& p, int dtype);
 int st_bigsplit(const ConvParams& p, hipStream_t stream);
-extern int g_opt_bigsplit;  // STTS_OPT_BIGSPLIT
 // C = 64 resblock convs on the bigconv2 engine with 128-frame wave slices (bf16 and / or ST_SPLIT, STTS_OPT_BIG64)
 bool st_big64_eligible(const ConvParams& p, int dtype);
 int st_big64(const ConvParams& p, int dtype, hipStream_t stream);
-extern int g_opt_big64;
 int st_conv1d_engine(const ConvParams& p, int dtype);
 // resblock conv engine (resconv.hip): bf16, C = 32 / 64, 1-D 'same' dilated conv with the
 // AdaIN + Snake prologue.  st_conv1d routes eligible launches to it while g_opt_resconv != 0.
 bool st_resconv_eligible(const ConvParams& p, int dtype);
 int st_resconv(const ConvParams& p, hipStream_t stream);
-extern int g_opt_rcpp;  // STTS_OPT_RCPP
-extern int g_opt_rcocc;  // STTS_OPT_RCOCC
 bool st_resconv_ups_eligible(const ConvParams& p, int dtype);
 int st_resconv_ups(const ConvParams& p, hipStream_t stream);
-extern int g_opt_resconv;
-extern int g_opt_small_tiles;  // few-tile igemm launches use 64 x 128 tiles (STTS_OPT_SMALL_TILES)
-extern int g_opt_grid_cap;  // > 0: cap persistent conv grids (tests: many tiles per block)
-extern int g_opt_debug;     // resconv phase-skipping knob (timing experiments only)
 extern unsigned long long* g_dbg_stamps;  // stts_set_debug_buffer (diagnostics only)
 // wide-stage resblock conv engine (bigconv.hip): bf16, C = 128 / 256, same contract
 bool st_bigconv_eligible(const ConvParams& p, int dtype);
@@ -140,35 +131,23 @@ int st_bigconv(const ConvParams& p, hipStream_t stream);
 // barrier per 32-channel group); st_bigconv routes to it while g_opt_bigconv == 2 (the default)
 bool st_bigconv2_eligible(const ConvParams& p);
 int st_bigconv2(const ConvParams& p, hipStream_t stream);
-extern int g_opt_bigconv;
-extern int g_opt_exp;   // STTS_OPT_EXP (bigconv2.hip, resconv.hip): the reference layouts of three bitwise tests
 // the decoder front-end's k3 AdainResBlk1d convs on the bigconv2 engine (STTS_OPT_FRONT)
 bool st_front_eligible(const ConvParams& p, int dtype);
 int st_bigconv2_front(const ConvParams& p, hipStream_t stream);
 // the HiFi-GAN ups[0] / ups[1] polyphase upsamplers on the bigconv2 engine (STTS_OPT_UPS)
-extern int g_opt_ups;
-extern int g_opt_wgw;
-extern int g_opt_bf16f;
-extern int g_opt_yf32;  // STTS_OPT_YF32 (convbwd.hip)
-extern int g_opt_cout1;  // STTS_OPT_COUT1 (convbwd.hip)
-extern int g_opt_plainrc;  // resconv.hip: prologue-free C = 32 / 64 convs (training step) on resconv (STTS_OPT_PLAINRC)  // convbwd.hip: bf16 weight gradient of stride-1 convs on k_wgrad_bf16w (STTS_OPT_WGRAD)
 bool st_ups_eligible(const ConvParams& p, int dtype);
 int st_bigconv2_ups(const ConvParams& p, hipStream_t stream);
-extern int g_opt_front;
 // HiFi-GAN output head (head.hip): Snake -> conv_post (C -> 1, 7 taps) -> tanh as one streaming pass;
 // st_conv1d routes eligible launches to it while g_opt_head != 0
 bool st_head_eligible(const ConvParams& p);
 int st_head(const ConvParams& p, int dtype, hipStream_t stream);
-extern int g_opt_head;
 // short-conv GEMM engine (pwgemm.hip): bf16, 1 tap (2 with g_opt_pw == 2), N % 64 == 0, [AdaIN / Snake /
 // LReLU] prologue, bias / residual / GELU / statistics epilogue; st_conv1d routes eligible launches to it
 bool st_pw_eligible(const ConvParams& p, int dtype);
 int st_pw(const ConvParams& p, hipStream_t stream);
 // its split-K path for small launches (tiles < CUs / 2, >= 8 chunks, 1-3 'same' taps): needs splitk_ws
 bool st_pw_split_eligible(const ConvParams& p, int dtype);
-extern int g_opt_splitk;  // STTS_OPT_SPLITK
 int st_pw_split(const ConvParams& p, hipStream_t stream);
-extern int g_opt_pw;
 
 // ---------------------------------------------------------------- misc kernels
 // src [B][C][L] fp32 (torch NCL) -> dst frames [B][L][ld] at channel offset c0; optional stats.
@@ -229,8 +208,6 @@ size_t st_packed_conv_elems(int Cin, int Cout, int K, int transposed, int u);
 int st_frames_to_f32(const void* src, int B, int L, int C, int ld, float* dst, int dtype, hipStream_t s);
 // acc = ((acc + rs[0]) + rs[1] ...) / div over n contiguous elements (the concurrent resblock branches' average)
 int st_branch_avg(void* acc, const void* const* rs, int nr, float div, long long n, int dtype, hipStream_t s);
-extern int g_opt_branches;  // STTS_OPT_BRANCHES (plan.cpp)
-extern int g_opt_nbranch;   // STTS_OPT_NBRANCH (plan.cpp)
 // GAN losses over the MPD engine's outputs (misc.hip): per (period, layer) block, its offset, the
 // size of its real half, and whether it is a score block (conv_post)
 constexpr int kMpdMaxSegs = 64;

@@ -533,7 +533,6 @@ int build_mpd(Model& m, const int* cfg, int n) {
 // each 4 weight-norm Conv2d (3, 9) [strides (1,1), (1,2) x 3] + Conv2d (3, 3) + out Conv2d(32, 1, 3)
 // (:38-45), cfg = {n, (n_fft, hop, win) x n}
 constexpr int kMsdCh = 32;
-int g_opt_msdfold = 1;  // STTS_OPT_MSDFOLD, read when an MSD model is created
 int build_msd(Model& m, const int* cfg, int n) {
   if (n < 4 || (n - 1) != 3 * cfg[0]) return ST_EINVAL;
   m.msd.resize(cfg[0]);
@@ -573,14 +572,26 @@ MsdGeom msd_geom(const Model::DiscS& d, int Tn) {
   return g;
 }
 
-long long msd_out_elems(const Model& m, int S, int Tn) {
-  long long n = 0;
+// The feature maps one discriminator forward over B signals writes to its flat `out` buffer, in output order (6 per
+// period / resolution, the last of them the score map): the one statement of that order and of the sizes, which
+// the forwards, stts_*_out_elems and the GAN losses all read.
+struct DiscMap {
+  long long off, elems;  // start in `out`, size (both in floats, for the B signals the list was made for)
+  bool score;
+};
+using DiscMaps = std::vector<DiscMap>;
+long long maps_elems(const DiscMaps& v) { return v.empty() ? 0 : v.back().off + v.back().elems; }  // of all maps
+void add_map(DiscMaps& v, long long elems, bool score) { v.push_back({maps_elems(v), elems, score}); }
+
+DiscMaps msd_maps(const Model& m, int S, int Tn) {
+  DiscMaps v;
+  v.reserve(6 * m.msd.size());
   for (const auto& d : m.msd) {
     const MsdGeom g = msd_geom(d, Tn);
-    for (int j = 1; j <= 5; ++j) n += (long long)S * g.H * g.W[j] * kMsdCh;
-    n += (long long)S * g.H * g.W[5];
+    for (int j = 1; j <= 5; ++j) add_map(v, (long long)S * g.H * g.W[j] * kMsdCh, false);
+    add_map(v, (long long)S * g.H * g.W[5], true);
   }
-  return n;
+  return v;
 }
 
 // per-layer frame counts of DiscriminatorP(p) over Tn samples: L[0] = ceil(Tn / p), then the 4
@@ -591,15 +602,16 @@ void mpd_lengths(int Tn, int p, int (&L)[6]) {
   L[5] = L[4];
 }
 
-long long mpd_out_elems(const Model& m, int B, int Tn) {
-  long long n = 0;
+DiscMaps mpd_maps(const Model& m, int B, int Tn) {
+  DiscMaps v;
+  v.reserve(6 * m.mpd.size());
   for (const auto& d : m.mpd) {
     int L[6];
     mpd_lengths(Tn, d.period, L);
-    for (int j = 0; j < 5; ++j) n += (long long)B * d.period * L[j + 1] * kMpdCh[j + 1];
-    n += (long long)B * d.period * L[5];
+    for (int j = 1; j <= 5; ++j) add_map(v, (long long)B * d.period * L[j] * kMpdCh[j], false);
+    add_map(v, (long long)B * d.period * L[5], true);
   }
-  return n;
+  return v;
 }
 
 void finalize_layout(Model& m) {
@@ -661,8 +673,6 @@ struct Buf {
   int ld = 0, L = 0;
   void* at(int c0, size_t esz) const { return p + (size_t)c0 * esz; }
 };
-
-static int g_opt_stats_slots = 0;  // STTS_OPT_STATS_SLOTS (0 = automatic)
 
 struct Ctx {
   Model* m;
@@ -1410,7 +1420,8 @@ int vocos_forward(Ctx& c, const DecIO& io) {
 int mpd_forward(Ctx& c, const float* wave, int Tn, float* out) {
   Model& m = *c.m;
   const int B0 = c.B;
-  size_t off = 0;
+  const DiscMaps maps = mpd_maps(m, B0, Tn);
+  size_t k = 0;  // the map being written
   for (const auto& d : m.mpd) {
     const int p = d.period;
     int L[6];
@@ -1428,21 +1439,22 @@ int mpd_forward(Ctx& c, const float* wave, int Tn, float* out) {
       q.epi_lrelu = 1;
       q.epi_slope = 0.1f;  // LRELU_SLOPE (discriminators.py:9)
       RUN(conv_run(c, q));
-      RUN(st_frames_to_f32(y.p, c.B, L[j + 1], kMpdCh[j + 1], y.ld, out ? out + off : nullptr, c.dtype, c.s));
-      off += (size_t)c.B * L[j + 1] * kMpdCh[j + 1];
+      RUN(st_frames_to_f32(y.p, c.B, L[j + 1], kMpdCh[j + 1], y.ld, out ? out + maps[k].off : nullptr, c.dtype,
+                           c.s));
+      ++k;
       x = y;
     }
     {
       ConvParams q = conv_base(c, d.post, x, 0);
       q.pad = 1;
       q.Lq = L[5];
-      q.y = out ? out + off : nullptr;
+      q.y = out ? out + maps[k].off : nullptr;
       q.y_bs = L[5];
       q.y_ld = 1;
       q.y_f32 = 1;
       q.Lout = L[5];
       RUN(conv_run(c, q));
-      off += (size_t)c.B * L[5];
+      ++k;
     }
     c.B = B0;
   }
@@ -1461,7 +1473,8 @@ int mpd_forward(Ctx& c, const float* wave, int Tn, float* out) {
 int msd_forward(Ctx& c, const float* wave, int Tn, float* out) {
   Model& m = *c.m;
   const int S = c.B;
-  size_t off = 0;
+  const DiscMaps maps = msd_maps(m, S, Tn);
+  size_t k = 0;  // the map being written
   for (const auto& d : m.msd) {
     const MsdGeom g = msd_geom(d, Tn);
     c.B = S * g.H;  // the conv batch: every (signal, frame) row of bins
@@ -1484,8 +1497,8 @@ int msd_forward(Ctx& c, const float* wave, int Tn, float* out) {
       q.epi_lrelu = 1;
       q.epi_slope = 0.1f;  // LRELU_SLOPE (discriminators.py:9)
       RUN(conv_run(c, q));
-      RUN(st_frames_to_f32(y.p, c.B, g.W[j + 1], kMsdCh, kMsdCh, out ? out + off : nullptr, c.dtype, c.s));
-      off += (size_t)c.B * g.W[j + 1] * kMsdCh;
+      RUN(st_frames_to_f32(y.p, c.B, g.W[j + 1], kMsdCh, kMsdCh, out ? out + maps[k].off : nullptr, c.dtype, c.s));
+      ++k;
       // the next layer's input; a folded (stride-2) next layer reads an even number of rows per sequence
       const int fnext = j + 1 < 5 ? d.convs[j + 1].fold : 0;
       const int We = fnext ? (g.W[j + 1] + fnext - 1) / fnext * fnext : g.W[j + 1];
@@ -1496,13 +1509,13 @@ int msd_forward(Ctx& c, const float* wave, int Tn, float* out) {
       ConvParams q = conv_base(c, d.out, x3, 0);
       q.pad = 1;
       q.Lq = g.W[5];
-      q.y = out ? out + off : nullptr;
+      q.y = out ? out + maps[k].off : nullptr;
       q.y_bs = g.W[5];
       q.y_ld = 1;
       q.y_f32 = 1;
       q.Lout = g.W[5];
       RUN(conv_run(c, q));
-      off += (size_t)c.B * g.W[5];
+      ++k;
     }
     c.B = S;
   }
@@ -1809,6 +1822,53 @@ int with_ctx(Model* m, int dtype, int B, void* ws, long long ws_bytes, void* str
   return body(r);
 }
 
+// The model kinds: how stts_model_create builds one and which forward sizes its workspace (the dry run takes no
+// inputs or outputs).  A new kind is one row here and its typed forward entry point.
+struct Kind {
+  int kind;
+  int (*build)(Model&, const int*, int);
+  int (*dry)(Ctx&, int T);
+};
+DecIO dry_io(int T) {
+  DecIO io{};
+  io.T = T;
+  return io;
+}
+int dry_decoder(Ctx& c, int T) { return decoder_forward(c, dry_io(T)); }
+const Kind kKinds[] = {
+    {STTS_KIND_HIFIGAN, build_decoder, dry_decoder},
+    {STTS_KIND_ISTFTNET, build_decoder, dry_decoder},
+    {STTS_KIND_F0N, build_f0n, [](Ctx& c, int T) { return f0n_forward(c, nullptr, nullptr, T, nullptr, nullptr); }},
+    {STTS_KIND_STYLE, build_style, [](Ctx& c, int T) { return style_forward(c, nullptr, T, nullptr); }},
+    {STTS_KIND_MPD, build_mpd, [](Ctx& c, int T) { return mpd_forward(c, nullptr, T, nullptr); }},
+    {STTS_KIND_VOCOS, build_vocos, [](Ctx& c, int T) { return vocos_forward(c, dry_io(T)); }},
+    {STTS_KIND_MSD, build_msd, [](Ctx& c, int T) { return msd_forward(c, nullptr, T, nullptr); }},
+    {STTS_KIND_PITCH, build_pitch,
+     [](Ctx& c, int T) { return pitch_forward(c, nullptr, T, nullptr, nullptr, nullptr, nullptr); }},
+};
+const Kind* find_kind(int kind) {
+  for (const Kind& k : kKinds)
+    if (k.kind == kind) return &k;
+  return nullptr;
+}
+
+// stts_mpd_losses / stts_msd_losses over the maps of B real then B generated signals (`maps` made for B: a map's real
+// half is its size, and the pair starts at twice its offset)
+int disc_losses(const DiscMaps& maps, const float* out, double* scratch, long long scratch_bytes, double* loss,
+                void* stream) {
+  MpdLossSegs sg;
+  memset(&sg, 0, sizeof(sg));
+  for (const DiscMap& mp : maps) {
+    if (sg.n >= kMpdMaxSegs) return ST_EINVAL;
+    sg.off[sg.n] = 2 * mp.off;
+    sg.half[sg.n] = mp.elems;
+    sg.score[sg.n] = mp.score;
+    ++sg.n;
+  }
+  if (scratch_bytes < (long long)sg.n * kMpdLossBlocks * 4 * (long long)sizeof(double)) return ST_EWORKSPACE;
+  return st_mpd_losses(out, sg, scratch, loss, (hipStream_t)stream);
+}
+
 }  // namespace
 
 // ======================================================================= C-ABI
@@ -1817,23 +1877,11 @@ extern "C" {
 int stts_model_create(int kind, const int* cfg, int ncfg, stts_model** out) {
   if (!out || (ncfg > 0 && !cfg)) return ST_EINVAL;
   *out = nullptr;
+  const Kind* k = find_kind(kind);
+  if (!k) return ST_EINVAL;
   Model* m = new Model();
   m->kind = kind;
-  int r = ST_EINVAL;
-  if (kind == STTS_KIND_HIFIGAN || kind == STTS_KIND_ISTFTNET)
-    r = build_decoder(*m, cfg, ncfg);
-  else if (kind == STTS_KIND_F0N)
-    r = build_f0n(*m, cfg, ncfg);
-  else if (kind == STTS_KIND_STYLE)
-    r = build_style(*m, cfg, ncfg);
-  else if (kind == STTS_KIND_MPD)
-    r = build_mpd(*m, cfg, ncfg);
-  else if (kind == STTS_KIND_VOCOS)
-    r = build_vocos(*m, cfg, ncfg);
-  else if (kind == STTS_KIND_MSD)
-    r = build_msd(*m, cfg, ncfg);
-  else if (kind == STTS_KIND_PITCH)
-    r = build_pitch(*m, cfg, ncfg);
+  const int r = k->build(*m, cfg, ncfg);
   if (r != 0) {
     delete m;
     return r;
@@ -1882,33 +1930,11 @@ int stts_pack(stts_model* m, int dtype, void* packed, long long bytes, void* str
 
 long long stts_workspace_bytes(const stts_model* mc, int dtype, int B, int T) {
   if (!mc || B <= 0 || T <= 0) return ST_EINVAL;
-  Model* m = const_cast<Model*>(mc);
+  const Kind* k = find_kind(mc->kind);
+  if (!k) return ST_EINVAL;
   size_t need = 0;
-  int r;
-  if (m->kind == STTS_KIND_HIFIGAN || m->kind == STTS_KIND_ISTFTNET) {
-    DecIO io{};
-    io.T = T;
-    r = with_ctx(m, dtype, B, nullptr, 0, nullptr, [&](Ctx& c) { return decoder_forward(c, io); }, &need);
-  } else if (m->kind == STTS_KIND_F0N) {
-    r = with_ctx(m, dtype, B, nullptr, 0, nullptr,
-                 [&](Ctx& c) { return f0n_forward(c, nullptr, nullptr, T, nullptr, nullptr); }, &need);
-  } else if (m->kind == STTS_KIND_MPD) {
-    r = with_ctx(m, dtype, B, nullptr, 0, nullptr, [&](Ctx& c) { return mpd_forward(c, nullptr, T, nullptr); },
-                 &need);
-  } else if (m->kind == STTS_KIND_MSD) {
-    r = with_ctx(m, dtype, B, nullptr, 0, nullptr, [&](Ctx& c) { return msd_forward(c, nullptr, T, nullptr); },
-                 &need);
-  } else if (m->kind == STTS_KIND_VOCOS) {
-    DecIO io{};
-    io.T = T;
-    r = with_ctx(m, dtype, B, nullptr, 0, nullptr, [&](Ctx& c) { return vocos_forward(c, io); }, &need);
-  } else if (m->kind == STTS_KIND_PITCH) {
-    r = with_ctx(m, dtype, B, nullptr, 0, nullptr,
-                 [&](Ctx& c) { return pitch_forward(c, nullptr, T, nullptr, nullptr, nullptr, nullptr); }, &need);
-  } else {
-    r = with_ctx(m, dtype, B, nullptr, 0, nullptr, [&](Ctx& c) { return style_forward(c, nullptr, T, nullptr); },
-                 &need);
-  }
+  const int r = with_ctx(const_cast<Model*>(mc), dtype, B, nullptr, 0, nullptr, [&](Ctx& c) { return k->dry(c, T); },
+                         &need);
   return r ? r : (long long)need;
 }
 
@@ -1965,7 +1991,7 @@ int stts_log_norm(const float* mel, int B, int n_mels, int T, float mean, float 
 
 long long stts_mpd_out_elems(const stts_model* m, int B, int T) {
   if (!m || m->kind != STTS_KIND_MPD || B <= 0 || T <= 0) return ST_EINVAL;
-  return mpd_out_elems(*m, B, T);
+  return maps_elems(mpd_maps(*m, B, T));
 }
 
 int stts_mpd_fwd(stts_model* m, int dtype, const float* wave, int B, int T, float* out, long long out_elems,
@@ -1974,7 +2000,7 @@ int stts_mpd_fwd(stts_model* m, int dtype, const float* wave, int B, int T, floa
   if (B <= 0 || !wave || !out) return ST_EINVAL;
   for (const auto& d : m->mpd)  // the reference's reflect pad needs the pad < T
     if (T < 2 || (T + d.period - 1) / d.period * d.period - T >= T) return ST_EINVAL;
-  if (out_elems < mpd_out_elems(*m, B, T)) return ST_EINVAL;
+  if (out_elems < maps_elems(mpd_maps(*m, B, T))) return ST_EINVAL;
   ST_CHECK(check_params(*m));
   return with_ctx(m, dtype, B, ws, ws_bytes, stream, [&](Ctx& c) { return mpd_forward(c, wave, T, out); }, nullptr);
 }
@@ -1983,34 +2009,17 @@ int stts_mpd_fwd(stts_model* m, int dtype, const float* wave, int B, int T, floa
 // layer) segment (6 per period / resolution)
 long long stts_gan_losses_scratch_bytes(const stts_model* m) {
   if (!m) return ST_EINVAL;
-  long long segs;
-  if (m->kind == STTS_KIND_MPD) segs = 6LL * (long long)m->mpd.size();
-  else if (m->kind == STTS_KIND_MSD) segs = 6LL * (long long)m->msd.size();
+  size_t segs;  // (the number of maps depends on neither the batch nor the length)
+  if (m->kind == STTS_KIND_MPD) segs = mpd_maps(*m, 1, 1).size();
+  else if (m->kind == STTS_KIND_MSD) segs = msd_maps(*m, 1, 1).size();
   else return ST_EINVAL;
-  return segs * kMpdLossBlocks * 4 * (long long)sizeof(double);
+  return (long long)segs * kMpdLossBlocks * 4 * (long long)sizeof(double);
 }
 
 int stts_mpd_losses(const stts_model* m, int B, int T, const float* out, double* scratch,
                     long long scratch_bytes, double* loss, void* stream) {
   if (!m || m->kind != STTS_KIND_MPD || B <= 0 || T <= 0 || !out || !scratch || !loss) return ST_EINVAL;
-  MpdLossSegs sg;
-  memset(&sg, 0, sizeof(sg));
-  long long off = 0;
-  for (const auto& d : m->mpd) {
-    int L[6];
-    mpd_lengths(T, d.period, L);
-    for (int j = 0; j < 6; ++j) {
-      if (sg.n >= kMpdMaxSegs) return ST_EINVAL;
-      const long long half = (long long)B * d.period * L[j < 5 ? j + 1 : 5] * kMpdCh[j < 5 ? j + 1 : 0];
-      sg.off[sg.n] = off;
-      sg.half[sg.n] = half;
-      sg.score[sg.n] = j == 5;
-      ++sg.n;
-      off += 2 * half;
-    }
-  }
-  if (scratch_bytes < (long long)sg.n * kMpdLossBlocks * 4 * (long long)sizeof(double)) return ST_EWORKSPACE;
-  return st_mpd_losses(out, sg, scratch, loss, (hipStream_t)stream);
+  return disc_losses(mpd_maps(*m, B, T), out, scratch, scratch_bytes, loss, stream);
 }
 
 // MultiResolutionSTFTLoss (losses.py:55-94): workspace = the per-resolution partial sums (fixed-order
@@ -2048,7 +2057,7 @@ int stts_mrstft_loss(const float* x, const float* y, int B, long long L, long lo
 
 long long stts_msd_out_elems(const stts_model* m, int B, int T) {
   if (!m || m->kind != STTS_KIND_MSD || B <= 0 || T <= 0) return ST_EINVAL;
-  return msd_out_elems(*m, B, T);
+  return maps_elems(msd_maps(*m, B, T));
 }
 
 int stts_msd_fwd(stts_model* m, int dtype, const float* wave, int B, int T, float* out, long long out_elems,
@@ -2057,7 +2066,7 @@ int stts_msd_fwd(stts_model* m, int dtype, const float* wave, int B, int T, floa
   if (B <= 0 || !wave || !out) return ST_EINVAL;
   for (const auto& d : m->msd)  // torch.stft's reflect pad needs n_fft / 2 < T
     if (T <= d.n_fft / 2) return ST_EINVAL;
-  if (out_elems < msd_out_elems(*m, B, T)) return ST_EINVAL;
+  if (out_elems < maps_elems(msd_maps(*m, B, T))) return ST_EINVAL;
   ST_CHECK(check_params(*m));
   return with_ctx(m, dtype, B, ws, ws_bytes, stream, [&](Ctx& c) { return msd_forward(c, wave, T, out); }, nullptr);
 }
@@ -2065,23 +2074,7 @@ int stts_msd_fwd(stts_model* m, int dtype, const float* wave, int B, int T, floa
 int stts_msd_losses(const stts_model* m, int B, int T, const float* out, double* scratch,
                     long long scratch_bytes, double* loss, void* stream) {
   if (!m || m->kind != STTS_KIND_MSD || B <= 0 || T <= 0 || !out || !scratch || !loss) return ST_EINVAL;
-  MpdLossSegs sg;
-  memset(&sg, 0, sizeof(sg));
-  long long off = 0;
-  for (const auto& d : m->msd) {
-    const MsdGeom g = msd_geom(d, T);
-    for (int j = 1; j <= 6; ++j) {
-      if (sg.n >= kMpdMaxSegs) return ST_EINVAL;
-      const long long half = (long long)B * g.H * g.W[j < 6 ? j : 5] * (j < 6 ? kMsdCh : 1);
-      sg.off[sg.n] = off;
-      sg.half[sg.n] = half;
-      sg.score[sg.n] = j == 6;
-      ++sg.n;
-      off += 2 * half;
-    }
-  }
-  if (scratch_bytes < (long long)sg.n * kMpdLossBlocks * 4 * (long long)sizeof(double)) return ST_EWORKSPACE;
-  return st_mpd_losses(out, sg, scratch, loss, (hipStream_t)stream);
+  return disc_losses(msd_maps(*m, B, T), out, scratch, scratch_bytes, loss, stream);
 }
 
 long long stts_mel_frames(long long L) { return st_mel_frames(L); }
@@ -2107,79 +2100,9 @@ const char* stts_error_string(int code) {
   }
 }
 
-int stts_set_option(int key, int value) {
-  switch (key) {
-    case STTS_OPT_RESCONV: g_opt_resconv = value != 0; return 0;
-    case STTS_OPT_GRID_CAP: g_opt_grid_cap = value > 0 ? value : 0; return 0;
-    case STTS_OPT_DEBUG: g_opt_debug = value; return 0;
-    case STTS_OPT_STATS_SLOTS: g_opt_stats_slots = value > 0 ? value : 0; return 0;
-    case STTS_OPT_SMALL_TILES: g_opt_small_tiles = value != 0; return 0;
-    case STTS_OPT_BIGCONV: g_opt_bigconv = (value >= 1 && value <= 5) ? value : 2; return 0;
-    case STTS_OPT_HEAD: g_opt_head = value ? 1 : 0; return 0;
-    case STTS_OPT_FRONT: g_opt_front = (value >= 0 && value <= 2) ? value : 1; return 0;
-    case STTS_OPT_PW: g_opt_pw = (value >= 0 && value <= 2) ? value : 1; return 0;
-    case STTS_OPT_SPLITK: g_opt_splitk = value ? 1 : 0; return 0;
-    case STTS_OPT_EXP: g_opt_exp = value; return 0;
-    case STTS_OPT_UPS: g_opt_ups = (value >= 0 && value <= 2) ? value : 1; return 0;
-    case STTS_OPT_WGRAD: g_opt_wgw = value ? 1 : 0; return 0;
-    case STTS_OPT_PLAINRC: g_opt_plainrc = value ? 1 : 0; return 0;
-    case STTS_OPT_MSDFOLD: g_opt_msdfold = value ? 1 : 0; return 0;
-    case STTS_OPT_RCPP: g_opt_rcpp = (value >= 0 && value <= 3) ? value : 1; return 0;
-    case STTS_OPT_RESSPLIT: g_opt_ressplit = value ? 1 : 0; return 0;
-    case STTS_OPT_BIGSPLIT: g_opt_bigsplit = value; return 0;
-    case STTS_OPT_BIG64: g_opt_big64 = value; return 0;
-    case STTS_OPT_SEGPART: g_opt_segpart = value; return 0;
-    case STTS_OPT_RCOCC: g_opt_rcocc = value; return 0;
-    case STTS_OPT_BF16F: g_opt_bf16f = value ? 1 : 0; return 0;
-    case STTS_OPT_YF32: g_opt_yf32 = value ? 1 : 0; return 0;
-    case STTS_OPT_COUT1: g_opt_cout1 = value ? 1 : 0; return 0;
-    case STTS_OPT_BRANCHES:
-      if (value < 0) return ST_EINVAL;
-      g_opt_branches = value;
-      return 0;
-    case STTS_OPT_NBRANCH:
-      if (value < 0) return ST_EINVAL;
-      g_opt_nbranch = value;
-      return 0;
-    default: return ST_EINVAL;  // (unknown and retired keys)
-  }
-}
-
 int stts_set_debug_buffer(void* buf) {
   g_dbg_stamps = reinterpret_cast<unsigned long long*>(buf);
   return 0;
-}
-
-int stts_get_option(int key) {
-  switch (key) {
-    case STTS_OPT_RESCONV: return g_opt_resconv;
-    case STTS_OPT_GRID_CAP: return g_opt_grid_cap;
-    case STTS_OPT_DEBUG: return g_opt_debug;
-    case STTS_OPT_STATS_SLOTS: return g_opt_stats_slots;
-    case STTS_OPT_SMALL_TILES: return g_opt_small_tiles;
-    case STTS_OPT_BIGCONV: return g_opt_bigconv;
-    case STTS_OPT_HEAD: return g_opt_head;
-    case STTS_OPT_FRONT: return g_opt_front;
-    case STTS_OPT_PW: return g_opt_pw;
-    case STTS_OPT_SPLITK: return g_opt_splitk;
-    case STTS_OPT_EXP: return g_opt_exp;
-    case STTS_OPT_UPS: return g_opt_ups;
-    case STTS_OPT_WGRAD: return g_opt_wgw;
-    case STTS_OPT_PLAINRC: return g_opt_plainrc;
-    case STTS_OPT_MSDFOLD: return g_opt_msdfold;
-    case STTS_OPT_RCPP: return g_opt_rcpp;
-    case STTS_OPT_RESSPLIT: return g_opt_ressplit;
-    case STTS_OPT_BIGSPLIT: return g_opt_bigsplit;
-    case STTS_OPT_BIG64: return g_opt_big64;
-    case STTS_OPT_SEGPART: return g_opt_segpart;
-    case STTS_OPT_RCOCC: return g_opt_rcocc;
-    case STTS_OPT_BF16F: return g_opt_bf16f;
-    case STTS_OPT_YF32: return g_opt_yf32;
-    case STTS_OPT_COUT1: return g_opt_cout1;
-    case STTS_OPT_BRANCHES: return g_opt_branches;
-    case STTS_OPT_NBRANCH: return g_opt_nbranch;
-    default: return ST_EINVAL;
-  }
 }
 
 int stts_profile_enable(int on) {

@@ -427,8 +427,6 @@ __global__ void __launch_bounds__(256) k_pw_reduce(const ConvParams p, int S, co
 
 }  // namespace
 
-int g_opt_pw = 1;
-
 bool st_pw_eligible(const ConvParams& p, int dtype) {
   if (!g_opt_pw || dtype != ST_BF16) return false;
   // 2-tap launches (the polyphase upsamplers) only with STTS_OPT_PW = 2: one tile at a time, load ->
@@ -476,8 +474,6 @@ int st_pw(const ConvParams& p, hipStream_t stream) {
     hipLaunchKernelGGL(k_pwgemm<2>, dim3((unsigned)blocks), dim3(NT), lds, stream, q, ntm, ntn);
   return (int)hipGetLastError();
 }
-
-int g_opt_splitk = 1;
 
 bool st_pw_split_eligible(const ConvParams& p, int dtype) {
   if (!g_opt_pw || !g_opt_splitk || dtype != ST_BF16 || !p.splitk_ws) return false;

@@ -962,10 +962,6 @@ int launch_rc_k(const ConvParams& p, hipStream_t s) {
 
 }  // namespace
 
-int g_opt_plainrc = 1;
-int g_opt_rcpp = 3;
-int g_opt_rcocc = 1;
-
 bool st_resconv_eligible(const ConvParams& p, int dtype) {
   if (dtype != ST_BF16) return false;
   const int C = p.Cout;

@@ -430,8 +430,6 @@ int launch_rs_k(const ConvParams& p, hipStream_t s) {
 
 }  // namespace
 
-int g_opt_ressplit = 1;
-
 bool st_ressplit_eligible(const ConvParams& p, int dtype) {
   if (!g_opt_ressplit || dtype != ST_SPLIT) return false;
   const int C = p.Cout;

@@ -56,39 +56,15 @@ def lib():
     return L
 
 
-# (keys 3, 9, 26 and 28 are retired and never reused: include/stts2.h)
-OPT_RESCONV = 1
-OPT_GRID_CAP = 2
-OPT_DEBUG = 4
-OPT_STATS_SLOTS = 5
-OPT_SMALL_TILES = 6
-OPT_BIGCONV = 7
-OPT_HEAD = 8
-OPT_FRONT = 10
-OPT_PW = 11
-OPT_SPLITK = 12
-OPT_EXP = 13
-OPT_UPS = 14
-OPT_WGRAD = 15
-OPT_PLAINRC = 16
-OPT_MSDFOLD = 17
-OPT_RCPP = 18
-OPT_RESSPLIT = 19
-OPT_BF16F = 20
-OPT_YF32 = 21
-OPT_COUT1 = 22
-OPT_BRANCHES = 23
-OPT_NBRANCH = 24
-OPT_BIGSPLIT = 25
-OPT_BIG64 = 27
-OPT_SEGPART = 29
-OPT_RCOCC = 30
-# the production defaults of every STTS_OPT_* (include/stts2.h)
-OPT_DEFAULTS = {OPT_RESCONV: 1, OPT_GRID_CAP: 0, OPT_DEBUG: 0, OPT_STATS_SLOTS: 0,
-                OPT_SMALL_TILES: 1, OPT_BIGCONV: 2, OPT_HEAD: 1, OPT_FRONT: 1, OPT_PW: 1, OPT_SPLITK: 1,
-                OPT_EXP: 0, OPT_UPS: 1, OPT_WGRAD: 1, OPT_PLAINRC: 1, OPT_MSDFOLD: 1,
-                OPT_RCPP: 3, OPT_RESSPLIT: 1, OPT_BF16F: 0, OPT_YF32: 1, OPT_COUT1: 1, OPT_BRANCHES: 8, OPT_NBRANCH: 64,
-                OPT_BIGSPLIT: 1, OPT_BIG64: 5, OPT_SEGPART: 1, OPT_RCOCC: 1}
+# (name, key, production default) of every live STTS_OPT_* (include/stts2.h; csrc/options.h holds the library's rows).
+# Keys 3, 9, 26 and 28 are retired and never reused.
+_OPTS = (("RESCONV", 1, 1), ("GRID_CAP", 2, 0), ("DEBUG", 4, 0), ("STATS_SLOTS", 5, 0), ("SMALL_TILES", 6, 1),
+         ("BIGCONV", 7, 2), ("HEAD", 8, 1), ("FRONT", 10, 1), ("PW", 11, 1), ("SPLITK", 12, 1), ("EXP", 13, 0),
+         ("UPS", 14, 1), ("WGRAD", 15, 1), ("PLAINRC", 16, 1), ("MSDFOLD", 17, 1), ("RCPP", 18, 3), ("RESSPLIT", 19, 1),
+         ("BF16F", 20, 0), ("YF32", 21, 1), ("COUT1", 22, 1), ("BRANCHES", 23, 8), ("NBRANCH", 24, 64),
+         ("BIGSPLIT", 25, 1), ("BIG64", 27, 5), ("SEGPART", 29, 1), ("RCOCC", 30, 1))
+globals().update({"OPT_" + _n: _k for _n, _k, _ in _OPTS})  # OPT_RESCONV = 1, ...
+OPT_DEFAULTS = {_k: _d for _, _k, _d in _OPTS}
 # STTS_OPTS="KEY=VALUE,..." (A/B runs of whole suites): option values that replace the defaults for the process,
 # applied when the library loads and by reset_options()
 for _kv in filter(None, os.environ.get("STTS_OPTS", "").split(",")):
@@ -434,9 +410,31 @@ def mpd_lengths(T: int, p: int):
     return L
 
 
-class MPDEngine(_Engine):
+class _DiscEngine(_Engine):
+    """What the two discriminator engines share: the GAN losses of the last forward."""
+
+    LOSSES = None  # the subclass names its loss entry point
+
+    def gan_losses(self):
+        """losses.py:97-128 feature_loss, generator_loss[0], discriminator_loss[0] of the last
+        forward, whose batch was B real then B generated waveforms: device float64 tensor [3]."""
+        out, B2, T = self.last
+        if B2 % 2:
+            raise ValueError("the last forward's batch is not real + generated halves")
+        nb = int(lib().stts_gan_losses_scratch_bytes(self.model.h))
+        check(nb if nb < 0 else 0, "stts_gan_losses_scratch_bytes")
+        scratch = torch.empty(nb // 8, dtype=torch.float64, device=out.device)
+        loss = torch.empty(3, dtype=torch.float64, device=out.device)
+        check(getattr(lib(), self.LOSSES)(self.model.h, B2 // 2, T, _ptr(out), _ptr(scratch), nb, _ptr(loss),
+                                          _stream()), self.LOSSES)
+        return loss
+
+
+class MPDEngine(_DiscEngine):
     """HIP forward of Modules/discriminators.py MultiPeriodDiscriminator's DiscriminatorP stacks
     (reference :108-129): one batch of waveforms [B, 1, T] -> per period (scores [B, L*p], fmaps)."""
+
+    LOSSES = "stts_mpd_losses"
 
     def __init__(self, module, dtype="fp32"):
         super().__init__(module, dtype)
@@ -476,20 +474,6 @@ class MPDEngine(_Engine):
             res.append((score, fmaps))
         return res
 
-    def gan_losses(self):
-        """losses.py:97-128 feature_loss, generator_loss[0], discriminator_loss[0] of the last
-        forward, whose batch was B real then B generated waveforms: device float64 tensor [3]."""
-        out, B2, T = self.last
-        if B2 % 2:
-            raise ValueError("the last forward's batch is not real + generated halves")
-        nb = int(lib().stts_gan_losses_scratch_bytes(self.model.h))
-        check(nb if nb < 0 else 0, "stts_gan_losses_scratch_bytes")
-        scratch = torch.empty(nb // 8, dtype=torch.float64, device=out.device)
-        loss = torch.empty(3, dtype=torch.float64, device=out.device)
-        check(lib().stts_mpd_losses(self.model.h, B2 // 2, T, _ptr(out), _ptr(scratch), nb, _ptr(loss), _stream()),
-              "stts_mpd_losses")
-        return loss
-
 
 def msd_geometry(T, n_fft, hop):
     """SpecDiscriminator map sizes over T samples (plan.cpp:msd_geom): H frames, widths W[0..5]."""
@@ -501,9 +485,11 @@ def msd_geometry(T, n_fft, hop):
     return H, W
 
 
-class MSDEngine(_Engine):
+class MSDEngine(_DiscEngine):
     """HIP forward of Modules/discriminators.py MultiResSpecDiscriminator's SpecDiscriminator stacks
     (reference :47-63): one batch of waveforms [B, 1, T] -> per resolution (scores [B, H*W], fmaps)."""
+
+    LOSSES = "stts_msd_losses"
 
     def __init__(self, module, dtype="fp32"):
         super().__init__(module, dtype)
@@ -544,19 +530,6 @@ class MSDEngine(_Engine):
                 off += k
             res.append((torch.flatten(fmaps[-1], 1, -1), fmaps))  # discriminators.py:63
         return res
-
-    def gan_losses(self):
-        """losses.py:97-128 over the last forward's outputs (B real then B generated signals)."""
-        out, B2, T = self.last
-        if B2 % 2:
-            raise ValueError("the last forward's batch is not real + generated halves")
-        nb = int(lib().stts_gan_losses_scratch_bytes(self.model.h))
-        check(nb if nb < 0 else 0, "stts_gan_losses_scratch_bytes")
-        scratch = torch.empty(nb // 8, dtype=torch.float64, device=out.device)
-        loss = torch.empty(3, dtype=torch.float64, device=out.device)
-        check(lib().stts_msd_losses(self.model.h, B2 // 2, T, _ptr(out), _ptr(scratch), nb, _ptr(loss), _stream()),
-              "stts_msd_losses")
-        return loss
 
 
 N_MELS, MEL_HOP, MEL_NFFT = 80, 300, 2048

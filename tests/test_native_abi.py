@@ -3,8 +3,11 @@ signature table (stts2_mi355x/abi.py) and engine's constants agree with those he
 plans name exactly the reference state-dict keys (no GPU compute here)."""
 import ctypes
 import glob
+import json
 import os
 import re
+import subprocess
+import sys
 
 import pytest
 import torch
@@ -289,6 +292,114 @@ def test_retired_option_keys_are_invalid(key):
     assert key not in engine.OPT_DEFAULTS
     assert L.stts_set_option(key, 1) == -1  # STTS_EINVAL
     assert L.stts_get_option(key) == -1
+
+
+def test_option_semantics_are_the_recorded_ones():
+    """stts_set_option / stts_get_option accept, normalise and refuse exactly as the library did before the options
+    moved into one table: tests/golden/option_semantics.json (make_golden_options.py) holds, for every key live
+    then and every probe value, [rc of set, get afterwards], the key at its initial value before each probe.  A key
+    recorded there and no longer live must be retired (STTS_EINVAL both ways), as must the keys recorded invalid."""
+    L = E.lib()
+    with open(os.path.join(ROOT, "tests", "golden", "option_semantics.json")) as f:
+        rec = json.load(f)
+    probes = rec["probes"]
+    assert probes == [-2, -1, 0, 1, 2, 3, 4, 5, 6, 7, 64, 65, 1 << 20]
+    assert len(rec["live"]) == 26 and sorted(rec["invalid"]) == sorted(["3", "9", "26", "28", "999"])
+    bad = []
+    try:
+        for name, row in rec["live"].items():
+            key = row["key"]
+            assert len(row["results"]) == len(probes), name
+            for v, want in zip(probes, row["results"]):
+                if key in E.OPT_DEFAULTS:
+                    assert L.stts_set_option(key, row["initial"]) == 0, name
+                else:
+                    want = [-1, -1]
+                got = [L.stts_set_option(key, v), L.stts_get_option(key)]
+                if got != want:
+                    bad.append(f"STTS_OPT_{name} <- {v}: (rc, value) {got}, recorded {want}")
+        for key, rows in rec["invalid"].items():
+            for v, want in zip(probes, rows):
+                assert want == [-1, -1]
+                got = [L.stts_set_option(int(key), v), L.stts_get_option(int(key))]
+                if got != want:
+                    bad.append(f"key {key} <- {v}: (rc, value) {got}, recorded {want}")
+    finally:
+        E.reset_options()
+    assert not bad, "\n".join(bad)
+
+
+def test_fresh_library_holds_the_production_defaults():
+    """The library's own initialisers equal engine's production defaults: a fresh process (no STTS_OPTS) loads the
+    library, sets nothing and reads every key.  (test_option_defaults_are_the_documented_ones resets the options
+    first, so it cannot see an initialiser that disagrees with engine.OPT_DEFAULTS.)  No GPU is touched."""
+    code = ("import json, sys; sys.path.insert(0, sys.argv[1]); from stts2_mi355x import engine as E; L = E.lib(); "
+            "print(json.dumps({str(k): L.stts_get_option(k) for k in E.OPT_DEFAULTS}))")
+    env = {k: v for k, v in os.environ.items() if k != "STTS_OPTS"}
+    r = subprocess.run([sys.executable, "-c", code, os.path.join(ROOT, "styletts2-lite_amd")], env=env,
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    got = {int(k): v for k, v in json.loads(r.stdout.strip().splitlines()[-1]).items()}
+    production = {k: d for _, k, d in E._OPTS}  # (OPT_DEFAULTS before any STTS_OPTS override of this process)
+    assert len(production) == 26
+    assert got == production, {k: (got.get(k), d) for k, d in production.items() if got.get(k) != d}
+
+
+def _mpd_elems(B, T, p):
+    """Floats of DiscriminatorP(p)'s 6 maps over B signals of T samples, by engine's mirror of the geometry."""
+    Ls = E.mpd_lengths(T, p)
+    return sum(B * p * (Ls[j + 1] if j < 5 else Ls[5]) * E.MPD_CH[j + 1] for j in range(6))
+
+
+def _msd_elems(B, T, n_fft, hop):
+    H, W = E.msd_geometry(T, n_fft, hop)
+    return sum(B * H * (W[j + 1] if j < 5 else W[5]) * (32 if j < 5 else 1) for j in range(6))
+
+
+def _scratch_bytes(n):
+    return 6 * n * 64 * 4 * 8  # 6 maps per discriminator x 64 partial blocks x 4 sums x sizeof(double)
+
+
+def test_mpd_map_list_matches_the_python_mirror():
+    """stts_mpd_out_elems and the loss scratch size (both read plan.cpp's one map list) against engine.mpd_lengths /
+    MPD_CH, per period and for the five together; the (period, T) pairs stts_mpd_fwd refuses for the reflect pad
+    are left out."""
+    L = E.lib()
+    periods, Ts = (2, 3, 5, 7, 11), (2, 3, 7, 100, 1201)
+    legal = lambda p, T: T >= 2 and (-T) % p < T  # noqa: E731
+    checked = 0
+    for ps in [(p,) for p in periods] + [periods]:
+        rc, h = _plan(E.KIND_MPD, [len(ps), *ps])
+        assert rc == 0
+        assert L.stts_gan_losses_scratch_bytes(h) == _scratch_bytes(len(ps))
+        for B in (1, 2):
+            for T in Ts:
+                if all(legal(p, T) for p in ps):
+                    assert L.stts_mpd_out_elems(h, B, T) == sum(_mpd_elems(B, T, p) for p in ps), (ps, B, T)
+                    checked += 1
+        L.stts_model_destroy(h)
+    assert checked == 2 * (5 + 5 + 4 + 3 + 3 + 3)  # T = 2 is legal for periods 2, 3; T = 3 for 2, 3, 5; T >= 7 for all
+
+
+def test_msd_map_list_matches_the_python_mirror():
+    """stts_msd_out_elems and the loss scratch size against engine.msd_geometry, per resolution at its smallest legal
+    T (n_fft / 2 + 1) and at 2,400, and for the three together at 2,400."""
+    L = E.lib()
+    res = ((16, 4, 16), (1024, 120, 600), (2048, 240, 1200))
+    for rs in [(r,) for r in res] + [res]:
+        rc, h = _plan(E.KIND_MSD, [len(rs)] + [v for r in rs for v in r])
+        assert rc == 0
+        assert L.stts_gan_losses_scratch_bytes(h) == _scratch_bytes(len(rs))
+        for B in (1, 2):
+            for T in sorted({max(r[0] for r in rs) // 2 + 1, 2400}):
+                assert L.stts_msd_out_elems(h, B, T) == sum(_msd_elems(B, T, r[0], r[1]) for r in rs), (rs, B, T)
+        L.stts_model_destroy(h)
+
+
+@pytest.mark.parametrize("kind", [-1, 7, 9, 100])
+def test_unknown_kinds_rejected(kind):
+    rc, h = _plan(kind, [1])
+    assert rc == -1 and not h.value  # STTS_EINVAL, no model
 
 
 def test_bilstm_error_word_offset():
