@@ -116,30 +116,78 @@ struct Small {  // weight-norm conv folded to fp32 for a VALU kernel
   size_t off = 0;
 };
 
+// The small-batch decoder's side streams (decoder_forward): a stage's resblocks 1.. run on streams 0.., every noise
+// branch on stream NOISE.  Streams and events are made on first use and live as long as the model.
+struct SideStreams {
+  enum { N = 4, NOISE = 2, FORK = 0, JOIN = N, MARK = 2 * N, NEV = 2 * N + 8 };
+  hipStream_t st[N] = {};
+  hipEvent_t ev[NEV] = {};  // FORK + the first stream forked, JOIN + the stream joined, MARK + k
+  ~SideStreams() {
+    for (auto& s : st)
+      if (s) (void)hipStreamDestroy(s);
+    for (auto& e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  int record(int k, hipStream_t s) {
+    if (!ev[k]) ST_CHECK_HIP(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
+    return (int)hipEventRecord(ev[k], s);
+  }
+
+  // One forward's forks from its stream `main`.  It knows which side streams run ahead of `main`, and on scope exit
+  // joins those that are not joined back yet: an error return leaves no side-stream work outside a hipGraph capture
+  // or still writing the workspace after the call returns.
+  struct Forks {
+    SideStreams& r;
+    hipStream_t main;
+    bool ahead[N] = {};
+    int marked[N] = {};  // the last mark recorded on a stream that is ahead
+    ~Forks() {
+      for (int i = 0; i < N; ++i)
+        if (ahead[i]) (void)join(i);
+    }
+    // streams i0 .. i0 + n - 1 go on after everything queued so far on main
+    int fork(int i0, int n = 1) {
+      for (int i = i0; i < i0 + n; ++i)
+        if (!r.st[i]) ST_CHECK_HIP(hipStreamCreateWithFlags(&r.st[i], hipStreamNonBlocking));
+      ST_CHECK(r.record(FORK + i0, main));
+      for (int i = i0; i < i0 + n; ++i) {
+        ST_CHECK_HIP(hipStreamWaitEvent(r.st[i], r.ev[FORK + i0], 0));
+        ahead[i] = true;
+        marked[i] = -1;
+      }
+      return 0;
+    }
+    // main goes on after everything queued so far on stream i
+    int join(int i) {
+      ahead[i] = false;
+      ST_CHECK(r.record(JOIN + i, r.st[i]));
+      return (int)hipStreamWaitEvent(main, r.ev[JOIN + i], 0);
+    }
+    // a join in two halves: mark k is a point on stream i that main waits for later (the noise branches: one mark
+    // per stage, reused across forwards); waiting for the stream's last mark joins it
+    int mark(int i, int k) {
+      marked[i] = k;
+      return r.record(MARK + k, r.st[i]);
+    }
+    int wait(int i, int k) {
+      if (marked[i] == k) ahead[i] = false;
+      return (int)hipStreamWaitEvent(main, r.ev[MARK + k], 0);
+    }
+  };
+};
+
 }  // namespace
 
 struct stts_model {
   int kind = 0;
   Params P;
-  // small-batch decoder: the stage's resblocks 1.. on side streams (decoder_forward), created on first use
-  hipStream_t side[4] = {};
-  hipEvent_t ev_fork = nullptr, ev_join[4] = {}, ev_fork2 = nullptr, ev_noise[8] = {};
+  SideStreams side;
   // the side streams and events are per model: concurrent forwards of one model (with their own workspaces and
   // streams) take turns through the forks and joins, so each wait sees its own forward's record
   std::mutex branch_mu;
   stts_model() = default;
   stts_model(const stts_model&) = delete;
   stts_model& operator=(const stts_model&) = delete;
-  ~stts_model() {
-    for (auto& s : side)
-      if (s) (void)hipStreamDestroy(s);
-    if (ev_fork) (void)hipEventDestroy(ev_fork);
-    if (ev_fork2) (void)hipEventDestroy(ev_fork2);
-    for (auto& e : ev_join)
-      if (e) (void)hipEventDestroy(e);
-    for (auto& e : ev_noise)
-      if (e) (void)hipEventDestroy(e);
-  }
   // -------- decoder config
   int dim_in = 512, style_dim = 128, init_ch = 512, n_fft = 0, hop = 0;
   std::vector<int> rates, kernels, rbk;
@@ -672,6 +720,8 @@ struct Buf {
   long long bs = 0;  // batch stride (elements)
   int ld = 0, L = 0;
   void* at(int c0, size_t esz) const { return p + (size_t)c0 * esz; }
+  // the same memory seen as L_ rows of ld_ per batch entry
+  Buf view(int L_, int ld_) const { return Buf{p, (long long)L_ * ld_, ld_, L_}; }
 };
 
 struct Ctx {
@@ -708,12 +758,16 @@ struct Ctx {
     return p;
   }
   Buf frames(int L, int ld) {
-    Buf b;
-    b.L = L;
-    b.ld = ld;
-    b.bs = (long long)L * ld;
+    Buf b = Buf().view(L, ld);
     b.p = alloc((size_t)B * L * ld * esz);
     return b;
+  }
+  // n equally sized temporaries of `elems` elements per batch entry; a stage sees them through Buf::view
+  void temps(Buf* g, int n, long long elems) {
+    for (int i = 0; i < n; ++i) {
+      g[i].p = alloc((size_t)B * elems * esz);
+      g[i].bs = elems;
+    }
   }
   double* stat(int C) {
     double* p = dry ? nullptr : reinterpret_cast<double*>(ws + stats_off);
@@ -788,6 +842,34 @@ void conv_out(ConvParams& p, Ctx& c, const Buf& y, int c0, int Lout) {
   p.y_ld = y.ld;
   p.Lout = Lout;
 }
+void conv_res(ConvParams& p, Ctx& c, const Buf& r, int c0 = 0) {  // + r (from channel c0) in the epilogue
+  p.res = r.at(c0, c.esz);
+  p.res_bs = r.bs;
+  p.res_ld = r.ld;
+}
+void conv_acc(ConvParams& p, const Buf& a) {  // + the running sum a
+  p.accb = a.p;
+  p.acc_bs = a.bs;
+  p.acc_ld = a.ld;
+}
+void conv_stats(ConvParams& p, double* st, int ld) {  // the output's InstanceNorm statistics into st
+  p.stats = st;
+  p.stats_ld = ld;
+}
+
+// runs `call` with the launches going to side stream i and the split-K partials to that stream's scratch; c.s and
+// c.splitk are put back on every path
+template <typename F>
+int on_side(Ctx& c, int i, float* splitk, F&& call) {
+  const hipStream_t s0 = c.s;
+  float* const splitk0 = c.splitk;
+  if (!c.dry) c.s = c.m->side.st[i];
+  c.splitk = splitk;
+  const int rc = call();
+  c.s = s0;
+  c.splitk = splitk0;
+  return rc;
+}
 
 // hipEvent pair around one profiled launch (stts_profile_*)
 int prof_begin(Ctx& c) {
@@ -836,35 +918,33 @@ int conv_run(Ctx& c, ConvParams& p) {
   return 0;
 }
 
+// front-end buffers (hifigan.py:458-472); X0 = decode.3's output [B][2T][512].  H1, SC, POOL are adain_blk's
+// temporaries (the F0/N stacks fill those three alone)
+struct FrontBufs {
+  Buf ENC, CAT[2], H1, SC, POOL, X0;
+  int ld_enc = 0, ld_cat = 0;
+};
+
 // AdainResBlk1d forward (hifigan.py:390-403).  x frames (ld, L); output into y at channel c0.
 int adain_blk(Ctx& c, const AdainBlk& k, const Buf& x, int xc0, const double* st_x, int st_x_ld, const Buf& y,
-              int yc0, double* st_y, int st_y_ld, Buf& H1, Buf& SC, Buf& POOL) {
+              int yc0, double* st_y, int st_y_ld, const FrontBufs& f) {
   const int L = x.L, Lr = k.up ? 2 * L : L;
   const float slope = 0.2f;
   // shortcut: conv1x1 at the input rate (nearest x2 commutes with a 1x1 conv)
+  const Buf sc = f.SC.view(L, k.cout);
   if (k.learned) {
     ConvParams p = conv_base(c, k.sc, x, xc0);
     p.Lq = L;
-    Buf sc = SC;
-    sc.ld = k.cout;
-    sc.L = L;
-    sc.bs = (long long)L * k.cout;
     conv_out(p, c, sc, 0, L);
     RUN(conv_run(c, p));
   }
   // residual: norm1 -> lrelu -> [pool] -> conv1
-  Buf h1 = H1;
-  h1.ld = k.cout;
-  h1.L = Lr;
-  h1.bs = (long long)Lr * k.cout;
+  const Buf h1 = f.H1.view(Lr, k.cout);
   double* st_h1 = c.stat(k.cout);
   {
     ConvParams p;
     if (k.up) {
-      Buf pool = POOL;
-      pool.ld = rup8(k.cin);
-      pool.L = Lr;
-      pool.bs = (long long)Lr * pool.ld;
+      const Buf pool = f.POOL.view(Lr, rup8(k.cin));
       Prologue pr = pro_adain(c, k.n1, st_x, st_x_ld, L, PRO_LRELU, -1, slope);
       RUN(st_pool_dw(x.at(xc0, c.esz), x.bs, x.ld, c.B, L, k.cin, c.aux_f(k.pool_off), c.P(k.pool_b), pr, pool.p,
                      pool.bs, pool.ld, c.dtype, c.s));
@@ -876,8 +956,7 @@ int adain_blk(Ctx& c, const AdainBlk& k, const Buf& x, int xc0, const double* st
     p.pad = 1;
     p.Lq = Lr;
     conv_out(p, c, h1, 0, Lr);
-    p.stats = st_h1;
-    p.stats_ld = k.cout;
+    conv_stats(p, st_h1, k.cout);
     RUN(conv_run(c, p));
   }
   // norm2 -> lrelu -> conv2, + shortcut, / sqrt(2)
@@ -887,19 +966,11 @@ int adain_blk(Ctx& c, const AdainBlk& k, const Buf& x, int xc0, const double* st
     p.pad = 1;
     p.Lq = Lr;
     conv_out(p, c, y, yc0, Lr);
-    if (k.learned) {
-      p.res = SC.p;
-      p.res_bs = (long long)L * k.cout;
-      p.res_ld = k.cout;
-    } else {
-      p.res = x.at(xc0, c.esz);
-      p.res_bs = x.bs;
-      p.res_ld = x.ld;
-    }
+    if (k.learned) conv_res(p, c, sc);
+    else conv_res(p, c, x, xc0);
     p.res_shift = k.up ? 1 : 0;
     p.out_scale = (float)(1.0 / sqrt(2.0));
-    p.stats = st_y;
-    p.stats_ld = st_y_ld;
+    conv_stats(p, st_y, st_y_ld);
     RUN(conv_run(c, p));
   }
   return 0;
@@ -923,8 +994,7 @@ int resblock1(Ctx& c, const ResBlock1& rb, const Buf& X, const double* st_x, Buf
       p.pad = rb.dil[d] * (rb.K - 1) / 2;
       p.Lq = L;
       conv_out(p, c, XT, 0, L);
-      p.stats = st_xt;
-      p.stats_ld = C;
+      conv_stats(p, st_xt, C);
       RUN(conv_run(c, p));
     }
     {
@@ -932,24 +1002,19 @@ int resblock1(Ctx& c, const ResBlock1& rb, const Buf& X, const double* st_x, Buf
       p.pro = pro_adain(c, rb.a2[d], st_xt, C, L, PRO_SNAKE, rb.al2[d], 0.f);
       p.pad = (rb.K - 1) / 2;
       p.Lq = L;
-      p.res = xc->p;
-      p.res_bs = xc->bs;
-      p.res_ld = xc->ld;
+      conv_res(p, c, *xc);
       const bool final = d == 2;
       if (final && ro != RO_PLAIN) {
         conv_out(p, c, *ACC, 0, L);
         if (ro != RO_ACC_FIRST) {
-          p.accb = ACC->p;
-          p.acc_bs = ACC->bs;
-          p.acc_ld = ACC->ld;
+          conv_acc(p, *ACC);
           if (ro == RO_ACC_LAST) p.acc_div = (float)nk;
         }
       } else {
         conv_out(p, c, R, 0, L);
         if (!final) {
           double* st_r = c.stat(C);
-          p.stats = st_r;
-          p.stats_ld = C;
+          conv_stats(p, st_r, C);
           st_c = st_r;
         }
       }
@@ -969,21 +1034,17 @@ struct DecIO {
   float* out;
 };
 
-// front-end buffers (hifigan.py:458-472); X0 = decode.3's output [B][2T][512]
-struct FrontBufs {
-  Buf ENC, CAT[2], H1, SC, POOL, X0;
-};
-
 FrontBufs alloc_front(Ctx& c, int T) {
   Model& m = *c.m;
-  const int ld_enc = rup8(m.dim_in + 2), ld_cat = rup8(1024 + 2 + 64);
   FrontBufs f;
-  f.ENC = c.frames(T, ld_enc);
-  f.CAT[0] = c.frames(T, ld_cat);
-  f.CAT[1] = c.frames(T, ld_cat);
+  f.ld_enc = rup8(m.dim_in + 2);
+  f.ld_cat = rup8(1024 + 2 + 64);
+  f.ENC = c.frames(T, f.ld_enc);
+  f.CAT[0] = c.frames(T, f.ld_cat);
+  f.CAT[1] = c.frames(T, f.ld_cat);
   f.H1 = c.frames(2 * T, 1024);
   f.SC = c.frames(T, 1024);
-  f.POOL = c.frames(2 * T, ld_cat);
+  f.POOL = c.frames(2 * T, f.ld_cat);
   f.X0 = c.frames(2 * T, 512);
   c.H = reinterpret_cast<float*>(c.alloc((size_t)c.B * m.Htot * 4));
   c.alloc_splitk((long long)T * 1024);  // the largest front-end conv output: T x 1024 = 2T x 512
@@ -995,8 +1056,8 @@ FrontBufs alloc_front(Ctx& c, int T) {
 int run_front(Ctx& c, const DecIO& io, FrontBufs& f) {
   Model& m = *c.m;
   const int B = c.B, T = io.T, n = 2 * T;
-  const int ld_enc = rup8(m.dim_in + 2), ld_cat = rup8(1024 + 2 + 64);
-  Buf &ENC = f.ENC, *CAT = f.CAT, &H1 = f.H1, &SC = f.SC, &POOL = f.POOL, &X0 = f.X0;
+  const int ld_enc = f.ld_enc, ld_cat = f.ld_cat;
+  Buf &ENC = f.ENC, *CAT = f.CAT;
   if (!c.h_ready) RUN(st_linear(io.s, B, m.style_dim, c.aux_f(m.wt_off), c.aux_f(m.bcat_off), m.Htot, c.H, c.s));
   double* S_enc = c.stat(ld_enc);
   RUN(st_ncl_to_frames(io.asr, B, m.dim_in, T, ENC.p, ld_enc, 0, ENC.bs, S_enc, ld_enc, c.dtype, c.s));
@@ -1015,10 +1076,7 @@ int run_front(Ctx& c, const DecIO& io, FrontBufs& f) {
     ConvParams p = conv_base(c, m.asr_res, ENC, 0);
     p.Lq = T;
     conv_out(p, c, CAT[w], 1024, T);
-    if (w == 0) {
-      p.stats = S_cat[0] + 1024 * ST_W;
-      p.stats_ld = ld_cat;
-    }
+    if (w == 0) conv_stats(p, S_cat[0] + 1024 * ST_W, ld_cat);
     RUN(conv_run(c, p));
     // these statistics are copied slot 0 only into the other concat buffers' stats below: fold
     if (w == 0 && c.slots > 1)
@@ -1029,335 +1087,265 @@ int run_front(Ctx& c, const DecIO& io, FrontBufs& f) {
       ST_CHECK_HIP(hipMemcpy2DAsync(S_cat[k] + 1024 * ST_W, (size_t)ld_cat * ST_W * 8, S_cat[0] + 1024 * ST_W,
                                     (size_t)ld_cat * ST_W * 8, 66 * ST_W * 8, B, hipMemcpyDeviceToDevice, c.s));
   }
-  ST_CHECK(adain_blk(c, m.encode, ENC, 0, S_enc, ld_enc, CAT[0], 0, S_cat[0], ld_cat, H1, SC, POOL));
-  ST_CHECK(adain_blk(c, m.decode[0], CAT[0], 0, S_cat[0], ld_cat, CAT[1], 0, S_cat[1], ld_cat, H1, SC, POOL));
-  ST_CHECK(adain_blk(c, m.decode[1], CAT[1], 0, S_cat[1], ld_cat, CAT[0], 0, S_cat[2], ld_cat, H1, SC, POOL));
-  ST_CHECK(adain_blk(c, m.decode[2], CAT[0], 0, S_cat[2], ld_cat, CAT[1], 0, S_cat[3], ld_cat, H1, SC, POOL));
-  ST_CHECK(adain_blk(c, m.decode[3], CAT[1], 0, S_cat[3], ld_cat, X0, 0, nullptr, 0, H1, SC, POOL));
+  ST_CHECK(adain_blk(c, m.encode, ENC, 0, S_enc, ld_enc, CAT[0], 0, S_cat[0], ld_cat, f));
+  ST_CHECK(adain_blk(c, m.decode[0], CAT[0], 0, S_cat[0], ld_cat, CAT[1], 0, S_cat[1], ld_cat, f));
+  ST_CHECK(adain_blk(c, m.decode[1], CAT[1], 0, S_cat[1], ld_cat, CAT[0], 0, S_cat[2], ld_cat, f));
+  ST_CHECK(adain_blk(c, m.decode[2], CAT[0], 0, S_cat[2], ld_cat, CAT[1], 0, S_cat[3], ld_cat, f));
+  ST_CHECK(adain_blk(c, m.decode[3], CAT[1], 0, S_cat[3], ld_cat, f.X0, 0, nullptr, 0, f));
   return 0;
 }
 
-int decoder_forward(Ctx& c, const DecIO& io) {
-  Model& m = *c.m;
-  const int B = c.B, T = io.T;
-  const bool ist = m.kind == STTS_KIND_ISTFTNET;
-  const int nup = (int)m.rates.size(), nrb = (int)m.rbk.size();
-  const size_t esz = c.esz;
-  // ---------------- allocations (identical in dry and real runs)
-  FrontBufs fb = alloc_front(c, T);
-  Buf& X0 = fb.X0;
-  const int n = 2 * T;
-  int scale = 1;
-  for (int r : m.rates) scale *= r;
-  if (ist) scale *= m.hop;
-  const int L = n * scale;
-  float* PH = reinterpret_cast<float*>(c.alloc((size_t)B * 9 * n * 4));
-  float* HAR = reinterpret_cast<float*>(c.alloc((size_t)B * L * 4));
-  // generator stage geometry
-  std::vector<int> Ls(nup), Cs(nup);
+// Everything decoder_forward allocates ahead of the statistics (alloc_decoder: identical in dry and real runs), with
+// the stage geometry and the side-stream decisions
+struct DecBufs {
+  FrontBufs fb;
+  bool ist = false, br = false, nbr = false;
+  int nup = 0, nrb = 0, scale = 1, L = 0;  // L output samples = 2T * scale
+  int F = 0, ld_h = 0;                     // istftnet: spectrogram frames, their leading dimension
+  std::vector<int> Ls, Cs;                 // stage s: Ls[s] rows of Cs[s] channels (the largest: smax elements)
   long long smax = 0;
-  {
-    int Lc = 2 * T;
-    for (int s = 0; s < nup; ++s) {
-      Lc *= m.rates[s];
-      Ls[s] = Lc + ((ist && s == nup - 1) ? 1 : 0);
-      Cs[s] = m.init_ch >> (s + 1);
-      smax = std::max(smax, (long long)Ls[s] * Cs[s]);
-    }
+  float *PH = nullptr, *HAR = nullptr;
+  Buf G[6], GB[8], NB[2];  // stage temporaries: the caller's stream, the resblock side streams, the noise stream
+  Buf HFR;                 // S-sample frames of the source for the MFMA noise_convs (largest such stage)
+  Buf HARF, POST, NSO[8];
+  float *splitk_br[4] = {}, *splitk_nb = nullptr;
+  Buf stage(const Buf& g, int s) const { return g.view(Ls[s], Cs[s]); }
+};
+
+DecBufs alloc_decoder(Ctx& c, int T) {
+  Model& m = *c.m;
+  const int B = c.B;
+  DecBufs b;
+  const bool ist = b.ist = m.kind == STTS_KIND_ISTFTNET;
+  const int nup = b.nup = (int)m.rates.size(), nrb = b.nrb = (int)m.rbk.size();
+  b.fb = alloc_front(c, T);
+  for (int r : m.rates) b.scale *= r;
+  if (ist) b.scale *= m.hop;
+  b.L = 2 * T * b.scale;
+  b.PH = reinterpret_cast<float*>(c.alloc((size_t)B * 9 * 2 * T * 4));
+  b.HAR = reinterpret_cast<float*>(c.alloc((size_t)B * b.L * 4));
+  // generator stage geometry
+  b.Ls.resize(nup);
+  b.Cs.resize(nup);
+  for (int s = 0, Lc = 2 * T; s < nup; ++s) {
+    Lc *= m.rates[s];
+    b.Ls[s] = Lc + ((ist && s == nup - 1) ? 1 : 0);
+    b.Cs[s] = m.init_ch >> (s + 1);
+    b.smax = std::max(b.smax, (long long)b.Ls[s] * b.Cs[s]);
   }
   if (c.cdtype == ST_SPLIT) {  // the fp32 partials of the two-pass C = 64 split resblock convs (ressplit.hip)
-    c.splitk_elems = (long long)B * smax;
-    c.splitk = reinterpret_cast<float*>(c.alloc((size_t)B * smax * 4));
+    c.splitk_elems = (long long)B * b.smax;
+    c.splitk = reinterpret_cast<float*>(c.alloc((size_t)B * b.smax * 4));
   }
-  Buf G[6];
-  for (int i = 0; i < 6; ++i) {
-    G[i].p = c.alloc((size_t)B * smax * esz);
-    G[i].bs = smax;
-  }
-  // small batches (STTS_OPT_BRANCHES, default B <= 8): a stage's resblocks 1 .. nrb-1 run beside resblock 0 on side streams, each
-  // with its own temporaries and output, averaged afterwards (st_branch_avg) instead of through the running sum:
-  // at B = 1 one resblock conv fills 64-512 workgroups, so three side by side fill the chip better.  Not in the
-  // split accuracy mode (its two-pass C = 64 convs share the one fp32 partial buffer)
-  const bool br = g_opt_branches > 0 && B <= g_opt_branches && nrb > 1 && nrb <= 5 && c.cdtype != ST_SPLIT;
-  Buf GB[8];
-  // each side-stream resblock also gets its own split-K scratch (the short-conv engine's fp32 partials,
-  // st_pw_split): branches that shared c.splitk would write and reduce their partial sums in the same memory
-  float* splitk_br[4] = {};
-  if (br) {
-    for (int i = 0; i < 2 * (nrb - 1); ++i) {
-      GB[i].p = c.alloc((size_t)B * smax * esz);
-      GB[i].bs = smax;
-    }
+  c.temps(b.G, 6, b.smax);
+  // small batches (STTS_OPT_BRANCHES, default B <= 8): a stage's resblocks 1 .. nrb-1 run beside resblock 0 on side
+  // streams, each with its own temporaries and output, averaged afterwards (st_branch_avg) instead of through the
+  // running sum: at B = 1 one resblock conv fills 64-512 workgroups, so three side by side fill the chip better.
+  // Not in the split accuracy mode (its two-pass C = 64 convs share the one fp32 partial buffer)
+  b.br = g_opt_branches > 0 && B <= g_opt_branches && nrb > 1 && nrb <= 5 && c.cdtype != ST_SPLIT;
+  if (b.br) {
+    c.temps(b.GB, 2 * (nrb - 1), b.smax);
+    // each side-stream resblock also gets its own split-K scratch (the short-conv engine's fp32 partials,
+    // st_pw_split): branches that shared c.splitk would write and reduce their partial sums in the same memory
     if (c.splitk_elems)
-      for (int j = 0; j + 1 < nrb; ++j) splitk_br[j] = reinterpret_cast<float*>(c.alloc((size_t)c.splitk_elems * 4));
+      for (int j = 0; j + 1 < nrb; ++j) b.splitk_br[j] = reinterpret_cast<float*>(c.alloc((size_t)c.splitk_elems * 4));
   }
-  Buf HFR;  // S-sample frames of the source for the MFMA noise_convs (largest such stage)
-  {
-    int rows = 0;
-    for (int s = 0; s < nup; ++s)
-      if (!ist && m.nc_mm[s].reframe) rows = std::max(rows, Ls[s] + 1);
-    if (rows) HFR = c.frames(rows, 32);
-    HFR.ld = 32;
-  }
-  const int F = ist ? L / m.hop + 1 : 0;
-  const int ld_h = ist ? rup8(m.n_fft + 2) : 0;
-  Buf HARF, POST;
+  int rows = 0;
+  for (int s = 0; s < nup; ++s)
+    if (!ist && m.nc_mm[s].reframe) rows = std::max(rows, b.Ls[s] + 1);
+  if (rows) b.HFR = c.frames(rows, 32);
   if (ist) {
-    HARF = c.frames(F, ld_h);
-    POST = c.frames(F, ld_h);
+    b.F = b.L / m.hop + 1;
+    b.ld_h = rup8(m.n_fft + 2);
+    b.HARF = c.frames(b.F, b.ld_h);
+    b.POST = c.frames(b.F, b.ld_h);
   }
   // small batches (with the resblock branches): every stage's noise branch (noise_convs -> noise_res, which reads
   // only the harmonic source) runs on a third side stream from the start, beside the front-end and the stages;
   // stage s's ups conv waits for its output (per-stage buffers NSO)
-  const bool nbr = (br || (g_opt_nbranch > 0 && B <= g_opt_nbranch && c.cdtype != ST_SPLIT)) && nup <= 8;
-  Buf NSO[8], NB[2];
-  float* splitk_nb = nullptr;  // the side stream's own split-K scratch (the front-end's short convs use c.splitk)
-  if (nbr) {
-    for (int s = 0; s < nup; ++s) NSO[s] = c.frames(Ls[s], Cs[s]);
-    for (int i = 0; i < 2; ++i) {
-      NB[i].p = c.alloc((size_t)B * smax * esz);
-      NB[i].bs = smax;
-    }
-    if (c.splitk_elems) splitk_nb = reinterpret_cast<float*>(c.alloc((size_t)c.splitk_elems * 4));
+  b.nbr = (b.br || (g_opt_nbranch > 0 && B <= g_opt_nbranch && c.cdtype != ST_SPLIT)) && nup <= 8;
+  if (b.nbr) {
+    for (int s = 0; s < nup; ++s) b.NSO[s] = c.frames(b.Ls[s], b.Cs[s]);
+    c.temps(b.NB, 2, b.smax);
+    // the side stream's own split-K scratch (the front-end's short convs use c.splitk)
+    if (c.splitk_elems) b.splitk_nb = reinterpret_cast<float*>(c.alloc((size_t)c.splitk_elems * 4));
   }
+  return b;
+}
+
+// noise branch of stage s (hifigan.py:330-331): noise_convs -> NS -> noise_res -> R
+int noise_branch(Ctx& c, const DecBufs& b, int s, const Buf& NS, Buf R, Buf XT) {
+  Model& m = *c.m;
+  const int B = c.B, L = b.L, C = b.Cs[s], Ls_ = b.Ls[s];
+  const bool last = s + 1 == b.nup;
+  double* S_ns = c.stat(C);
+  int sf = 1;
+  for (int j = s + 1; j < b.nup; ++j) sf *= m.rates[j];
+  if (!b.ist && m.nc_mm[s].reframe) {  // noise_convs[s] on the MFMA engine over S-sample frames
+    const int S = m.nc_mm[s].reframe;
+    const Buf hf = b.HFR.view(Ls_ + 1, 32);
+    RUN(st_har_frames(b.HAR, B, L, S, (S + 1) / 2, Ls_ + 1, 32, hf.p, c.dtype, c.s));
+    ConvParams p = conv_base(c, m.nc_mm[s], hf, 0);
+    p.Lq = Ls_;
+    conv_out(p, c, NS, 0, Ls_);
+    conv_stats(p, S_ns, C);
+    RUN(conv_run(c, p));
+  } else if (!b.ist) {
+    const int K = last ? 1 : 2 * sf, st = last ? 1 : sf, pd = last ? 0 : (sf + 1) / 2;
+    if ((K == 1 || K == 4 || K == 12) && C % 8 == 0 && 256 % (C / 8) == 0) {
+      RUN(st_noise_conv(b.HAR, B, L, c.P(m.nc_w[s]), c.P(m.nc_b[s]), C, K, st, pd, Ls_, NS.p, S_ns, c.dtype, c.s));
+    } else {
+      SmallConvDst d = {NS.p, NS.bs, C, 0, S_ns, C};
+      RUN(st_conv_cin1(b.HAR, L, L, B, c.P(m.nc_w[s]), c.P(m.nc_b[s]), C, K, st, pd, Ls_, &d, 1, c.dtype, c.s));
+    }
+  } else {
+    ConvParams p = conv_base(c, m.nc_conv[s], b.HARF, 0);
+    if (!last) {
+      p.stride = sf;
+      p.pad = (sf + 1) / 2;
+    }
+    p.Lq = Ls_;
+    conv_out(p, c, NS, 0, Ls_);
+    conv_stats(p, S_ns, C);
+    RUN(conv_run(c, p));
+  }
+  return resblock1(c, m.noise_res[s], NS, S_ns, R, XT, RO_PLAIN, nullptr, 0);
+}
+// ups of stage s: Snake(alpha_s) / LReLU(0.1) prologue, polyphase ConvTranspose1d of xin into X, + x_source XS in the
+// epilogue (hifigan.py:327-332), statistics into S_x
+int ups_conv(Ctx& c, const DecBufs& b, int s, const Buf& xin, const Buf& XS, const Buf& X, double* S_x) {
+  Model& m = *c.m;
+  const WConv& w = m.ups[s];
+  const int u = m.rates[s];
+  ConvParams p = conv_base(c, w, xin, 0);
+  p.Cin = xin.ld;
+  if (!b.ist) {
+    p.pro.mode = PRO_SNAKE;
+    p.pro.alpha = c.P(m.alphas[s]);
+  } else {
+    p.pro.mode = PRO_LRELU;
+    p.pro.slope = 0.1f;
+  }
+  const int padT = b.ist ? (w.K - u) / 2 : u / 2 + u % 2;
+  const int Lout = xin.L * u;
+  p.pad = w.taps() - 1;
+  p.Lq = (Lout - 1 + padT) / u + 1;
+  p.up = u;
+  p.opad = padT;
+  conv_out(p, c, X, 0, Lout);
+  if (b.ist && s + 1 == b.nup) {
+    p.y_row_off = 1;
+    p.reflect_front = 1;
+  }
+  conv_res(p, c, XS);
+  conv_stats(p, S_x, b.Cs[s]);
+  return conv_run(c, p);
+}
+
+// the resblocks of stage s over X (statistics S_x) and their average into ACC (hifigan.py:336-342)
+int stage_resblocks(Ctx& c, const DecBufs& b, SideStreams::Forks& fk, int s, const Buf& X, const double* S_x, Buf R,
+                    Buf XT, Buf ACC) {
+  const int nrb = b.nrb;
+  const ResBlock1* rb = &c.m->resblocks[(size_t)s * nrb];
+  if (!b.br) {  // one stream: the running sum, through the epilogue of each resblock's last conv
+    for (int j = 0; j < nrb; ++j) {
+      const int ro = j == 0 ? RO_ACC_FIRST : (j == nrb - 1 ? RO_ACC_LAST : RO_ACC_MID);
+      ST_CHECK(resblock1(c, rb[j], X, S_x, R, XT, ro, &ACC, nrb));
+    }
+    return 0;
+  }
+  // fork: side stream j - 1 runs resblock j after everything queued so far on the caller's stream
+  if (!c.dry) ST_CHECK(fk.fork(0, nrb - 1));
+  ST_CHECK(resblock1(c, rb[0], X, S_x, R, XT, RO_ACC_FIRST, &ACC, nrb));
+  const void* rs[4];
+  for (int j = 1; j < nrb; ++j) {
+    Buf Rj = b.stage(b.GB[2 * (j - 1)], s), XTj = b.stage(b.GB[2 * (j - 1) + 1], s);
+    ST_CHECK(on_side(c, j - 1, b.splitk_br[j - 1],
+                     [&] { return resblock1(c, rb[j], X, S_x, Rj, XTj, RO_PLAIN, nullptr, 0); }));
+    rs[j - 1] = Rj.p;
+  }
+  // join, then ACC = ((ACC + R_1) + R_2 ...) / nrb
+  if (!c.dry)
+    for (int j = 0; j + 1 < nrb; ++j) ST_CHECK(fk.join(j));
+  RUN(st_branch_avg(ACC.p, rs, nrb - 1, (float)nrb, (long long)c.B * X.L * X.ld, c.dtype, c.s));
+  return 0;
+}
+
+int output_head(Ctx& c, const DecBufs& b, const DecIO& io, const Buf& xin) {
+  Model& m = *c.m;
+  ConvParams p = conv_base(c, m.conv_post, xin, 0);
+  p.pad = 3;
+  p.Lq = xin.L;
+  if (!b.ist) {  // Snake(alpha_last) -> conv_post -> tanh  (hifigan.py:343-345)
+    p.pro.mode = PRO_SNAKE;
+    p.pro.alpha = c.P(m.alphas[b.nup]);
+    p.y = io.out;
+    p.y_bs = xin.L;
+    p.y_ld = 1;
+    p.y_f32 = 1;
+    p.Lout = xin.L;
+    p.epi_tanh = 1;
+    return conv_run(c, p);
+  }
+  // LReLU(0.01) -> conv_post -> exp/sin -> CustomSTFT.inverse (istftnet.py:569-573)
+  p.pro.mode = PRO_LRELU;
+  p.pro.slope = 0.01f;
+  conv_out(p, c, b.POST, 0, xin.L);
+  RUN(conv_run(c, p));
+  RUN(st_istft(b.POST.p, c.B, b.F, b.ld_h, m.n_fft, m.hop, c.P(m.stft_br), c.P(m.stft_bi), io.out, b.L, c.dtype,
+               c.s));
+  return 0;
+}
+
+// Decoder.forward (hifigan.py:446-475 / istftnet.py:692-721); after the front-end it reads as Generator.forward
+// (hifigan.py:321-347 / istftnet.py:542-575)
+int decoder_forward(Ctx& c, const DecIO& io) {
+  Model& m = *c.m;
+  const int B = c.B, n = 2 * io.T;
+  enum { NOISE = SideStreams::NOISE };
+  DecBufs b = alloc_decoder(c, io.T);
   c.stats_begin = c.stats_off = c.off;  // stats region follows; its size is known after the dry run
   // ---------------- harmonic source (hifigan.py:323-326 / istftnet.py:544-550)
-  RUN(st_sine_phase(io.f0, B, n, scale, PH, c.s));
-  RUN(st_sine_source(io.f0, PH, B, n, scale, c.P(m.l_lin_w), c.P(m.l_lin_b), io.noise, io.seed, io.utt, HAR, c.s));
-  if (ist) {
-    RUN(st_stft(HAR, B, L, m.n_fft, m.hop, c.P(m.stft_fr), c.P(m.stft_fi), HARF.p, ld_h, c.dtype, c.s));
+  RUN(st_sine_phase(io.f0, B, n, b.scale, b.PH, c.s));
+  RUN(st_sine_source(io.f0, b.PH, B, n, b.scale, c.P(m.l_lin_w), c.P(m.l_lin_b), io.noise, io.seed, io.utt, b.HAR,
+                     c.s));
+  if (b.ist) {
+    RUN(st_stft(b.HAR, B, b.L, m.n_fft, m.hop, c.P(m.stft_fr), c.P(m.stft_fi), b.HARF.p, b.ld_h, c.dtype, c.s));
   }
-  // noise branch of stage s (hifigan.py:330-331): noise_convs -> NS -> noise_res -> R
-  auto noise_branch = [&](int s, Buf NS, Buf R, Buf XT) -> int {
-    const int C = Cs[s], Ls_ = Ls[s];
-    const bool last = s + 1 == nup;
-    double* S_ns = c.stat(C);
-    int sf = 1;
-    for (int j = s + 1; j < nup; ++j) sf *= m.rates[j];
-    if (!ist && m.nc_mm[s].reframe) {  // noise_convs[s] on the MFMA engine over S-sample frames
-      const int S = m.nc_mm[s].reframe;
-      Buf hf = HFR;
-      hf.L = Ls_ + 1;
-      hf.bs = (long long)hf.L * 32;
-      RUN(st_har_frames(HAR, B, L, S, (S + 1) / 2, Ls_ + 1, 32, hf.p, c.dtype, c.s));
-      ConvParams p = conv_base(c, m.nc_mm[s], hf, 0);
-      p.Lq = Ls_;
-      conv_out(p, c, NS, 0, Ls_);
-      p.stats = S_ns;
-      p.stats_ld = C;
-      RUN(conv_run(c, p));
-    } else if (!ist) {
-      const int K = last ? 1 : 2 * sf, st = last ? 1 : sf, pd = last ? 0 : (sf + 1) / 2;
-      if ((K == 1 || K == 4 || K == 12) && C % 8 == 0 && 256 % (C / 8) == 0) {
-        RUN(st_noise_conv(HAR, B, L, c.P(m.nc_w[s]), c.P(m.nc_b[s]), C, K, st, pd, Ls_, NS.p, S_ns, c.dtype, c.s));
-      } else {
-        SmallConvDst d = {NS.p, NS.bs, C, 0, S_ns, C};
-        RUN(st_conv_cin1(HAR, L, L, B, c.P(m.nc_w[s]), c.P(m.nc_b[s]), C, K, st, pd, Ls_, &d, 1, c.dtype, c.s));
-      }
-    } else {
-      Buf hf = HARF;
-      ConvParams p = conv_base(c, m.nc_conv[s], hf, 0);
-      if (!last) {
-        p.stride = sf;
-        p.pad = (sf + 1) / 2;
-      }
-      p.Lq = Ls_;
-      conv_out(p, c, NS, 0, Ls_);
-      p.stats = S_ns;
-      p.stats_ld = C;
-      RUN(conv_run(c, p));
-    }
-    ST_CHECK(resblock1(c, m.noise_res[s], NS, S_ns, R, XT, RO_PLAIN, nullptr, 0));
-    return 0;
-  };
-  auto sview = [&](Buf g, int s) {
-    g.ld = Cs[s];
-    g.L = Ls[s];
-    g.bs = (long long)Ls[s] * Cs[s];
-    return g;
-  };
   std::unique_lock<std::mutex> branch_lock;
-  if ((br || nbr) && !c.dry) branch_lock = std::unique_lock<std::mutex>(m.branch_mu);
-  // forked side streams that are not joined back yet: an error return joins them (event on each side stream, the
-  // caller's stream waits), so that no side-stream work is left outside a hipGraph capture or still writing the
-  // workspace after the call returns
-  struct SideJoin {
-    hipStream_t main = nullptr;
-    hipStream_t s[4] = {};
-    hipEvent_t e[4] = {};
-    int n = 0;
-    void add(hipStream_t st, hipEvent_t ev) {
-      s[n] = st;
-      e[n] = ev;
-      ++n;
-    }
-    ~SideJoin() {
-      for (int i = 0; i < n; ++i) {
-        (void)hipEventRecord(e[i], s[i]);
-        (void)hipStreamWaitEvent(main, e[i], 0);
-      }
-    }
-  } join_noise, join_br;
-  join_noise.main = join_br.main = c.s;
-  if (nbr) {
+  if ((b.br || b.nbr) && !c.dry) branch_lock = std::unique_lock<std::mutex>(m.branch_mu);
+  SideStreams::Forks fk{m.side, c.s};
+  if (b.nbr) {
     // the noise branches' AdaIN layers read H (the style projections): computed before the fork
     RUN(st_linear(io.s, B, m.style_dim, c.aux_f(m.wt_off), c.aux_f(m.bcat_off), m.Htot, c.H, c.s));
     c.h_ready = true;
-    if (!c.dry) {
-      if (!m.side[2]) ST_CHECK_HIP(hipStreamCreateWithFlags(&m.side[2], hipStreamNonBlocking));
-      for (int s = 0; s < nup; ++s)
-        if (!m.ev_noise[s]) ST_CHECK_HIP(hipEventCreateWithFlags(&m.ev_noise[s], hipEventDisableTiming));
-      if (!m.ev_fork2) ST_CHECK_HIP(hipEventCreateWithFlags(&m.ev_fork2, hipEventDisableTiming));
-      ST_CHECK_HIP(hipEventRecord(m.ev_fork2, c.s));
-      ST_CHECK_HIP(hipStreamWaitEvent(m.side[2], m.ev_fork2, 0));
-      join_noise.add(m.side[2], m.ev_noise[nup - 1]);
-    }
-    const hipStream_t s0 = c.s;
-    float* const splitk0 = c.splitk;
-    for (int s = 0; s < nup; ++s) {
-      if (!c.dry) c.s = m.side[2];
-      c.splitk = splitk_nb;
-      const int rc = noise_branch(s, sview(NB[0], s), NSO[s], sview(NB[1], s));
-      c.splitk = splitk0;
-      if (rc == 0 && !c.dry) {
-        const int e = (int)hipEventRecord(m.ev_noise[s], c.s);
-        c.s = s0;
-        ST_CHECK(e);
-      }
-      c.s = s0;
-      ST_CHECK(rc);
+    if (!c.dry) ST_CHECK(fk.fork(NOISE));
+    for (int s = 0; s < b.nup; ++s) {
+      ST_CHECK(on_side(c, NOISE, b.splitk_nb, [&] {
+        return noise_branch(c, b, s, b.stage(b.NB[0], s), b.NSO[s], b.stage(b.NB[1], s));
+      }));
+      if (!c.dry) ST_CHECK(fk.mark(NOISE, s));  // stage s waits for this
     }
   }
   // ---------------- style projections + front-end (hifigan.py:458-472)
-  ST_CHECK(run_front(c, io, fb));
+  ST_CHECK(run_front(c, io, b.fb));
   // ---------------- generator stages
-  Buf xin = X0;
-  int Lcur = 2 * T, Ccur = 512;
-  int accsel = 4;
-  for (int s = 0; s < nup; ++s) {
-    const int u = m.rates[s], C = Cs[s], Ls_ = Ls[s];
-    const bool last = s + 1 == nup;
-    auto view = [&](Buf g) {
-      g.ld = C;
-      g.L = Ls_;
-      g.bs = (long long)Ls_ * C;
-      return g;
-    };
-    Buf R = view(G[1]), XT = view(G[2]), X = view(G[3]), ACC = view(G[accsel]);
+  Buf xin = b.fb.X0;
+  for (int s = 0; s < b.nup; ++s) {
+    Buf R = b.stage(b.G[1], s), XT = b.stage(b.G[2], s), X = b.stage(b.G[3], s), ACC = b.stage(b.G[4 + s % 2], s);
     Buf XS = R;  // x_source: the noise branch's output
-    if (nbr) {   // this stage's noise branch ran on the side stream
-      XS = NSO[s];
-      if (!c.dry) ST_CHECK_HIP(hipStreamWaitEvent(c.s, m.ev_noise[s], 0));
+    if (b.nbr) {  // this stage's noise branch ran on the side stream
+      XS = b.NSO[s];
+      if (!c.dry) ST_CHECK(fk.wait(NOISE, s));
     } else {
-      ST_CHECK(noise_branch(s, view(G[0]), R, XT));
+      ST_CHECK(noise_branch(c, b, s, b.stage(b.G[0], s), R, XT));
     }
-    // ups (+ x_source): Snake(alpha_s) / LReLU(0.1) prologue, polyphase ConvTranspose1d
-    double* S_x = c.stat(C);
-    {
-      const WConv& w = m.ups[s];
-      ConvParams p = conv_base(c, w, xin, 0);
-      p.Cin = Ccur;
-      if (!ist) {
-        p.pro.mode = PRO_SNAKE;
-        p.pro.alpha = c.P(m.alphas[s]);
-      } else {
-        p.pro.mode = PRO_LRELU;
-        p.pro.slope = 0.1f;
-      }
-      const int taps = w.taps();
-      const int padT = ist ? (w.K - u) / 2 : u / 2 + u % 2;
-      const int Lout = Lcur * u;
-      p.pad = taps - 1;
-      p.Lq = (Lout - 1 + padT) / u + 1;
-      p.up = u;
-      p.opad = padT;
-      conv_out(p, c, X, 0, Lout);
-      if (ist && last) {
-        p.y_row_off = 1;
-        p.reflect_front = 1;
-      }
-      p.res = XS.p;
-      p.res_bs = XS.bs;
-      p.res_ld = XS.ld;
-      p.stats = S_x;
-      p.stats_ld = C;
-      RUN(conv_run(c, p));
-    }
-    if (br) {
-      // fork: side stream j - 1 runs resblock j after everything queued so far on the caller's stream
-      if (!c.dry) {
-        for (int j = 0; j + 1 < nrb; ++j) {
-          if (!m.side[j]) ST_CHECK_HIP(hipStreamCreateWithFlags(&m.side[j], hipStreamNonBlocking));
-          if (!m.ev_join[j]) ST_CHECK_HIP(hipEventCreateWithFlags(&m.ev_join[j], hipEventDisableTiming));
-        }
-        if (!m.ev_fork) ST_CHECK_HIP(hipEventCreateWithFlags(&m.ev_fork, hipEventDisableTiming));
-        ST_CHECK_HIP(hipEventRecord(m.ev_fork, c.s));
-        for (int j = 0; j + 1 < nrb; ++j) {
-          ST_CHECK_HIP(hipStreamWaitEvent(m.side[j], m.ev_fork, 0));
-          join_br.add(m.side[j], m.ev_join[j]);
-        }
-      }
-      ST_CHECK(resblock1(c, m.resblocks[(size_t)s * nrb], X, S_x, R, XT, RO_ACC_FIRST, &ACC, nrb));
-      const hipStream_t s0 = c.s;
-      float* const splitk0 = c.splitk;
-      const void* rs[4];
-      for (int j = 1; j < nrb; ++j) {
-        Buf Rj = view(GB[2 * (j - 1)]), XTj = view(GB[2 * (j - 1) + 1]);
-        if (!c.dry) c.s = m.side[j - 1];
-        c.splitk = splitk_br[j - 1];
-        const int rc = resblock1(c, m.resblocks[(size_t)s * nrb + j], X, S_x, Rj, XTj, RO_PLAIN, nullptr, 0);
-        c.s = s0;
-        c.splitk = splitk0;
-        ST_CHECK(rc);
-        rs[j - 1] = Rj.p;
-      }
-      // join, then ACC = ((ACC + R_1) + R_2 ...) / nrb
-      if (!c.dry) {
-        join_br.n = 0;  // joined here
-        for (int j = 0; j + 1 < nrb; ++j) {
-          ST_CHECK_HIP(hipEventRecord(m.ev_join[j], m.side[j]));
-          ST_CHECK_HIP(hipStreamWaitEvent(c.s, m.ev_join[j], 0));
-        }
-      }
-      RUN(st_branch_avg(ACC.p, rs, nrb - 1, (float)nrb, (long long)B * Ls_ * C, c.dtype, c.s));
-    } else {
-      for (int j = 0; j < nrb; ++j) {
-        const int ro = nrb == 1 ? RO_ACC_FIRST : (j == 0 ? RO_ACC_FIRST : (j == nrb - 1 ? RO_ACC_LAST : RO_ACC_MID));
-        ST_CHECK(resblock1(c, m.resblocks[(size_t)s * nrb + j], X, S_x, R, XT, ro, &ACC, nrb));
-      }
-    }
+    double* S_x = c.stat(b.Cs[s]);
+    ST_CHECK(ups_conv(c, b, s, xin, XS, X, S_x));
+    ST_CHECK(stage_resblocks(c, b, fk, s, X, S_x, R, XT, ACC));
     xin = ACC;
-    Lcur = Ls_;
-    Ccur = C;
-    accsel = accsel == 4 ? 5 : 4;
   }
-  join_noise.n = 0;  // every stage waited for its noise branch: the side stream is joined
-  // ---------------- output head
-  if (!ist) {  // Snake(alpha_last) -> conv_post -> tanh  (hifigan.py:343-345)
-    ConvParams p = conv_base(c, m.conv_post, xin, 0);
-    p.pro.mode = PRO_SNAKE;
-    p.pro.alpha = c.P(m.alphas[nup]);
-    p.pad = 3;
-    p.Lq = Lcur;
-    p.y = io.out;
-    p.y_bs = Lcur;
-    p.y_ld = 1;
-    p.y_f32 = 1;
-    p.Lout = Lcur;
-    p.epi_tanh = 1;
-    RUN(conv_run(c, p));
-  } else {  // LReLU(0.01) -> conv_post -> exp/sin -> CustomSTFT.inverse (istftnet.py:569-573)
-    ConvParams p = conv_base(c, m.conv_post, xin, 0);
-    p.pro.mode = PRO_LRELU;
-    p.pro.slope = 0.01f;
-    p.pad = 3;
-    p.Lq = Lcur;
-    conv_out(p, c, POST, 0, Lcur);
-    RUN(conv_run(c, p));
-    RUN(st_istft(POST.p, B, F, ld_h, m.n_fft, m.hop, c.P(m.stft_br), c.P(m.stft_bi), io.out, L, c.dtype, c.s));
-  }
-  (void)esz;
-  return 0;
+  return output_head(c, b, io, xin);
 }
 
 // --------------------------------------------------------------------- Vocos forward
@@ -1392,9 +1380,7 @@ int vocos_forward(Ctx& c, const DecIO& io) {
       ConvParams p = conv_base(c, b.pw2, HI, 0);
       p.Lq = L;
       conv_out(p, c, *y, 0, L);
-      p.res = x->p;
-      p.res_bs = x->bs;
-      p.res_ld = x->ld;
+      conv_res(p, c, *x);
       RUN(conv_run(c, p));
     }
     std::swap(x, y);
@@ -1484,11 +1470,8 @@ int msd_forward(Ctx& c, const float* wave, int Tn, float* out) {
     for (int j = 0; j < 5; ++j) {
       Buf y = c.frames(g.W[j + 1], kMsdCh);
       const WConv& cw = d.convs[j];
-      Buf xin = x3;
-      if (cw.fold) {  // stride-2 layer, folded: [W_even / 2][2 x 96] rows of the same memory
-        xin.L = x3.L / cw.fold;
-        xin.ld = x3.ld * cw.fold;
-      }
+      // a folded stride-2 layer reads [W_even / 2][2 x 96] rows of the same memory
+      const Buf xin = cw.fold ? x3.view(x3.L / cw.fold, x3.ld * cw.fold) : x3;
       ConvParams q = conv_base(c, cw, xin, 0);
       q.stride = cw.fold ? 1 : ((j >= 1 && j <= 3) ? 2 : 1);
       q.pad = cw.fold ? cw.fpad : (j < 4 ? 4 : 1);
@@ -1529,7 +1512,10 @@ int f0n_forward(Ctx& c, const float* x, const float* s, int T, float* F0, float*
   const int B = c.B, d = m.d_hid;
   Buf XL = c.frames(T, d);
   Buf Y0 = c.frames(T, d), Y1 = c.frames(2 * T, d / 2), Y2 = c.frames(2 * T, d / 2);
-  Buf H1 = c.frames(2 * T, d), SC = c.frames(T, d), POOL = c.frames(2 * T, rup8(d));
+  FrontBufs t;
+  t.H1 = c.frames(2 * T, d);
+  t.SC = c.frames(T, d);
+  t.POOL = c.frames(2 * T, rup8(d));
   c.H = reinterpret_cast<float*>(c.alloc((size_t)B * m.Htot * 4));
   c.alloc_splitk((long long)T * d);  // the largest conv output of the stacks: T x d = 2T x d/2
   c.stats_begin = c.stats_off = c.off;
@@ -1540,9 +1526,9 @@ int f0n_forward(Ctx& c, const float* x, const float* s, int T, float* F0, float*
     AdainBlk* blk = br == 0 ? m.f0blk : m.nblk;
     double* S1 = c.stat(d);
     double* S2 = c.stat(d / 2);
-    ST_CHECK(adain_blk(c, blk[0], XL, 0, S0, d, Y0, 0, S1, d, H1, SC, POOL));
-    ST_CHECK(adain_blk(c, blk[1], Y0, 0, S1, d, Y1, 0, S2, d / 2, H1, SC, POOL));
-    ST_CHECK(adain_blk(c, blk[2], Y1, 0, S2, d / 2, Y2, 0, nullptr, 0, H1, SC, POOL));
+    ST_CHECK(adain_blk(c, blk[0], XL, 0, S0, d, Y0, 0, S1, d, t));
+    ST_CHECK(adain_blk(c, blk[1], Y0, 0, S1, d, Y1, 0, S2, d / 2, t));
+    ST_CHECK(adain_blk(c, blk[2], Y1, 0, S2, d / 2, Y2, 0, nullptr, 0, t));
     ConvParams p = conv_base(c, br == 0 ? m.f0_proj : m.n_proj, Y2, 0);
     p.Lq = 2 * T;
     p.y = br == 0 ? F0 : Nout;

@@ -345,6 +345,50 @@ def test_fresh_library_holds_the_production_defaults():
     assert got == production, {k: (got.get(k), d) for k, d in production.items() if got.get(k) != d}
 
 
+def test_decoder_workspace_bytes_are_the_recorded_ones():
+    """The decoder plans' dry run (every allocation and the statistics region: the workspace layout the kernels and
+    a captured graph see) sizes the workspace exactly as the library did before decoder_forward was split into
+    parts: tests/golden/plan_workspace.json (make_golden_plan.py) holds stts_workspace_bytes for hifigan / istftnet /
+    vocos x dtype 0, 1, 2 x B in (1, 4, 8, 9, 16, 64, 65) x T in (4, 16, 40) at the default options, and for each
+    kind at B = 2, T = 16 with the side streams off and with the noise stream alone.  Dry runs: no GPU."""
+    from test_vocos_cpu import make_vocos
+    L = E.lib()
+    with open(os.path.join(ROOT, "tests", "golden", "plan_workspace.json")) as f:
+        rec = json.load(f)
+    kinds = {"hifigan": E.KIND_HIFIGAN, "istftnet": E.KIND_ISTFTNET, "vocos": E.KIND_VOCOS}
+    want_cases = [[k, dt, B, T, 8, 64] for k in kinds for dt in (0, 1, 2) for B in (1, 4, 8, 9, 16, 64, 65)
+                  for T in (4, 16, 40)]
+    want_cases += [[k, dt, 2, 16, br, nbr] for k in kinds for dt in (0, 1, 2) for br, nbr in ((0, 0), (0, 64))]
+    assert [r[:6] for r in rec["rows"]] == want_cases  # the recorded cross product, whole and in order
+    assert E.OPT_DEFAULTS[E.OPT_BRANCHES] == 8 and E.OPT_DEFAULTS[E.OPT_NBRANCH] == 64
+    from stts2_mi355x.hifigan import Decoder as H
+    from stts2_mi355x.istftnet import Decoder as I
+    v = make_vocos()
+    cfgs = {"hifigan": _dec_cfg(H(dim_in=512, style_dim=128, dim_out=80, **HIFI_CFG), False),
+            "istftnet": _dec_cfg(I(dim_in=512, style_dim=128, dim_out=80, **ISTFT_CFG), True),
+            "vocos": [v.dim_in, v.style_dim, v.generator.intermediate_dim, v.generator.num_layers, v.generator.n_fft,
+                      v.generator.hop]}
+    assert rec["configs"] == cfgs  # the configs helpers.make_decoder / make_vocos build
+    plans = {}
+    bad = []
+    try:
+        for k, cfg in cfgs.items():
+            rc, plans[k] = _plan(kinds[k], cfg)
+            assert rc == 0, k
+        for k, dt, B, T, br, nbr, want in rec["rows"]:
+            assert want > 0
+            E.set_option(E.OPT_BRANCHES, br)
+            E.set_option(E.OPT_NBRANCH, nbr)
+            got = L.stts_workspace_bytes(plans[k], dt, B, T)
+            if got != want:
+                bad.append(f"{k} dtype {dt} B {B} T {T} BRANCHES {br} NBRANCH {nbr}: {got} bytes, recorded {want}")
+    finally:
+        E.reset_options()
+        for h in plans.values():
+            L.stts_model_destroy(h)
+    assert not bad, "\n".join(bad)
+
+
 def _mpd_elems(B, T, p):
     """Floats of DiscriminatorP(p)'s 6 maps over B signals of T samples, by engine's mirror of the geometry."""
     Ls = E.mpd_lengths(T, p)
