@@ -534,6 +534,7 @@ int stts_profile_enable(int on);
 int stts_profile_read(double* total_ms, long long* launches, double* alg_flops, double* alg_bytes);
 /* Launch i of the timed region: shape = {B, rows, N, Cin, taps, dilation, Lout,
  * res | acc<<1 | engine<<4} with engine 0 = conv1d_igemm, 1 = resconv, 2 = bigconv, 3 = retired (the fused resblock engine),
+ * 4 = head, 5 = pwgemm, 6 = ressplit, 7 = bigsplit (the split-operand bigconv2 variant),
  * ms_flops_bytes = {hipEvent ms, algorithmic flops, algorithmic bytes}. */
 int stts_profile_launch(long long i, int* shape, double* ms_flops_bytes);
 

@@ -495,8 +495,6 @@ __global__ void __launch_bounds__(512, 1) k_bigconv(const ConvParams p) {
   }  // tile ranges
 }
 
-int g_num_cu_bc = 0;
-
 template <int C, int K, int DIL, bool ACC>
 int launch_bc(const ConvParams& p, hipStream_t stream) {
   using G = BG<C, K, DIL>;
@@ -508,20 +506,12 @@ int launch_bc(const ConvParams& p, hipStream_t stream) {
     ST_CHECK_HIP(hipFuncSetAttribute((const void*)kern1, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
     attr = true;
   }
-  if (!g_num_cu_bc) {
-    int dev = 0;
-    ST_CHECK_HIP(hipGetDevice(&dev));
-    ST_CHECK_HIP(hipDeviceGetAttribute(&g_num_cu_bc, hipDeviceAttributeMultiprocessorCount, dev));
-  }
   const long long tiles = (long long)((p.Lq + G::BM - 1) / G::BM) * p.B;
+  StGrid g;
+  ST_CHECK(st_grid(p, tiles, 1, true, &g));
   ConvParams q = p;
-  const int seg = st_seg_choice(p, 1, g_num_cu_bc);
-  long long grid = g_num_cu_bc;
-  if (grid > (seg ? (long long)p.B * seg : tiles)) grid = seg ? (long long)p.B * seg : tiles;
-  if (g_opt_grid_cap > 0 && grid > g_opt_grid_cap) grid = g_opt_grid_cap;
-  const bool segk = seg > 0 && grid < (long long)p.B * seg;  // (one segment per workgroup = the plain even split)
-  q.seg = segk ? seg : 0;
-  hipLaunchKernelGGL(segk ? kern1 : kern0, dim3((unsigned)grid), dim3(G::NT), G::LDS, stream, q);
+  q.seg = g.seg;
+  hipLaunchKernelGGL(g.segk ? kern1 : kern0, dim3(g.grid), dim3(G::NT), G::LDS, stream, q);
   return (int)hipGetLastError();
 }
 
@@ -551,17 +541,7 @@ int launch_bc_k(const ConvParams& p, hipStream_t s) {
 }  // namespace
 
 bool st_bigconv_eligible(const ConvParams& p, int dtype) {
-  if (dtype != ST_BF16) return false;
-  const int C = p.Cout;
-  if (!(C == 128 || C == 256) || p.Cin != C || p.N != C || p.nchunks * 32 != C) return false;
-  if (!(p.KS == 3 || p.KS == 7 || p.KS == 11) || !(p.dil == 1 || p.dil == 3 || p.dil == 5)) return false;
-  if ((p.kw != 0 && p.kw != p.KS) || p.row_off != 0 || p.stride != 1 || p.up != 1 || p.opad != 0) return false;
-  if (p.pad != p.dil * (p.KS - 1) / 2 || p.Lq != p.Lout || p.Lq != p.Lin) return false;
-  if (p.y_row_off || p.y_f32 || p.epi_tanh || p.epi_lrelu || p.epi_gelu || p.reflect_front || p.zc_period || p.res_shift) return false;
-  if (p.pro.mode != (PRO_AFFINE | PRO_SNAKE) || !p.pro.alpha || !p.pro.stats || !p.pro.gamma) return false;
-  if (p.accb && p.stats) return false;
-  if (p.x_ld % 8 || p.y_ld % 8 || (p.res && p.res_ld % 8) || (p.accb && p.acc_ld % 8)) return false;
-  return true;
+  return dtype == ST_BF16 && st_resblock_shape(p, 128, 256, 8) && st_pro_adain_snake(p.pro);
 }
 
 int st_bigconv(const ConvParams& p, hipStream_t stream) {

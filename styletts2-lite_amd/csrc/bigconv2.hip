@@ -782,22 +782,12 @@ template <int C, int NW, int K, int DIL, bool RES, bool ACC, int PRO = PK_SNAKE,
           int CO = C, bool OFS = false, bool SP = false, int NF = 8, int NCB = 0>
 int launch_b2(const ConvParams& p, hipStream_t stream) {
   using G = B2<C, NW, K, DIL, PRO, CINP, UPS, CO, OFS, NF, NCB>;
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    ST_CHECK_HIP(hipGetDevice(&dev));
-    ST_CHECK_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-  }
   const long long tiles = (long long)((p.Lq + G::TM - 1) / G::TM) * G::NCH * p.B;
+  StGrid g;  // (only a launch with more segments than workgroups needs the range loop)
+  ST_CHECK(st_grid(p, tiles, G::BPC, true, &g));
   ConvParams q = p;
-  const int seg = st_seg_choice(p, 1, ncu * G::BPC);
-  long long grid = (long long)ncu * G::BPC;
-  if (grid > (seg ? (long long)p.B * seg : tiles)) grid = seg ? (long long)p.B * seg : tiles;
-  if (g_opt_grid_cap > 0 && grid > g_opt_grid_cap) grid = g_opt_grid_cap;
-  // one segment per workgroup: the segments are the even split of the plain kernel (every utterance has the same
-  // tile count), so only a launch with more segments than workgroups needs the range loop
-  const bool segk = seg > 0 && grid < (long long)p.B * seg;
-  q.seg = segk ? seg : 0;
+  q.seg = g.seg;
+  const bool segk = g.segk;
   auto kern = segk ? k_bigconv2<C, NW, K, DIL, RES, ACC, PRO, CINP, UPS, CO, OFS, SP, NF, NCB, true>
                    : k_bigconv2<C, NW, K, DIL, RES, ACC, PRO, CINP, UPS, CO, OFS, SP, NF, NCB, false>;
   static bool attr[2] = {false, false};
@@ -805,7 +795,7 @@ int launch_b2(const ConvParams& p, hipStream_t stream) {
     ST_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
     attr[segk] = true;
   }
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * NW), G::LDS, stream, q);
+  hipLaunchKernelGGL(kern, dim3(g.grid), dim3(64 * NW), G::LDS, stream, q);
   return (int)hipGetLastError();
 }
 
@@ -850,13 +840,9 @@ bool st_bigconv2_eligible(const ConvParams& p) {
   return true;  // on top of st_bigconv_eligible
 }
 
-static int b2_num_cu() {
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      ncu = 256;
-  }
+static int b2_num_cu() {  // (for the size rules below, which must answer without a device: 256 then)
+  int ncu = 256;
+  (void)st_num_cu(&ncu);
   return ncu;
 }
 
@@ -880,16 +866,18 @@ bool st_front_eligible(const ConvParams& p, int dtype) {
          (!p.res || (p.res_ld % 8 == 0 && (p.res_shift == 0 || p.res_shift == 1)));
 }
 
-int st_bigconv2_front(const ConvParams& p, hipStream_t s) {
+template <bool SP>  // (SP: the split-operand variant, st_bigsplit)
+static int b2_front(const ConvParams& p, hipStream_t s) {
   if (p.Cout == 1024)
-    return p.res ? launch_b2<1024, 8, 3, 1, true, false, PK_LRELU, FE_CINP>(p, s)
-                 : launch_b2<1024, 8, 3, 1, false, false, PK_LRELU, FE_CINP>(p, s);
+    return p.res ? launch_b2<1024, 8, 3, 1, true, false, PK_LRELU, FE_CINP, false, 1024, false, SP>(p, s)
+                 : launch_b2<1024, 8, 3, 1, false, false, PK_LRELU, FE_CINP, false, 1024, false, SP>(p, s);
   if (p.Cout == 512)
-    return p.res ? launch_b2<512, 8, 3, 1, true, false, PK_LRELU, FE_CINP>(p, s)
-                 : launch_b2<512, 8, 3, 1, false, false, PK_LRELU, FE_CINP>(p, s);
+    return p.res ? launch_b2<512, 8, 3, 1, true, false, PK_LRELU, FE_CINP, false, 512, false, SP>(p, s)
+                 : launch_b2<512, 8, 3, 1, false, false, PK_LRELU, FE_CINP, false, 512, false, SP>(p, s);
   return ST_EINVAL;
 }
 
+int st_bigconv2_front(const ConvParams& p, hipStream_t s) { return b2_front<false>(p, s); }
 
 int st_bigconv2(const ConvParams& p, hipStream_t stream) {
   // STTS_OPT_BIGCONV 5: C = 256 on 8-wave blocks with the second half one group behind (OFS; a third window
@@ -915,30 +903,30 @@ int st_bigconv2(const ConvParams& p, hipStream_t stream) {
 // x + x_source of :335): 2 taps, on this engine instead of conv1d_igemm (STTS_OPT_UPS, default on)
 
 bool st_ups_eligible(const ConvParams& p, int dtype) {
-  if (!g_opt_ups || dtype != ST_BF16 || p.up <= 1 || !p.res || p.accb) return false;
+  if (!g_opt_ups || dtype != ST_BF16 || p.up <= 1) return false;
   // (ups[2], N = 192: STTS_OPT_UPS 1 takes it too, 2 = ups[0] / ups[1] only)
   const bool shape = (p.N == 2560 && p.Cin == 512 && p.Cout == 256) || (p.N == 640 && p.Cin == 256 && p.Cout == 128) ||
                      (g_opt_ups == 1 && p.N == 192 && p.Cin == 128 && p.Cout == 64);
-  return shape && p.N == p.up * p.Cout && p.Cout % 16 == 0 && p.KS == 2 && (p.kw == 0 || p.kw == 2) &&
-         p.dil == 1 && p.stride == 1 && p.pad == 1 && p.row_off == 0 && p.pro.mode == PRO_SNAKE && p.pro.alpha &&
-         p.res_shift == 0 && p.y_row_off == 0 && !p.reflect_front && !p.epi_tanh && !p.epi_lrelu && !p.epi_gelu &&
-         !p.y_f32 && p.zc_period == 0 && p.x_ld % 8 == 0 && p.y_ld % 8 == 0 && p.res_ld % 8 == 0 &&
-         p.nchunks * 32 == p.Cin;
+  return shape && p.N == p.up * p.Cout && p.Cout % 16 == 0 && p.nchunks * 32 == p.Cin && st_polyphase_shape(p);
 }
 
-int st_bigconv2_ups(const ConvParams& p, hipStream_t s) {
-  if (p.N == 2560 && p.Cout == 256) return launch_b2<2560, 8, 2, 1, true, false, PK_SNAKE, 512, true, 256>(p, s);
-  if (p.N == 640 && p.Cout == 128) return launch_b2<640, 4, 2, 1, true, false, PK_SNAKE, 256, true, 128>(p, s);
+template <bool SP>  // (SP: the split-operand variant, st_bigsplit)
+static int b2_ups(const ConvParams& p, hipStream_t s) {
+  if (p.N == 2560 && p.Cout == 256) return launch_b2<2560, 8, 2, 1, true, false, PK_SNAKE, 512, true, 256, false, SP>(p, s);
+  if (p.N == 640 && p.Cout == 128) return launch_b2<640, 4, 2, 1, true, false, PK_SNAKE, 256, true, 128, false, SP>(p, s);
   // ups[2]: 12-wave blocks (three per SIMD) of all 6 output blocks (the 3 phases) x 2 frame slices of 128 frames, so each
-  // window is DMA'd and transformed once instead of once per phase: 668 -> 479 us (profiles/r05_ab_ups12.txt).
+  // window is DMA'd and transformed once instead of once per phase: 668 -> 479 us, split 1167 -> 926 us
+  // (profiles/r05_ab_ups12.txt).
   // STTS_OPT_EXP bit 32: 4-wave blocks of 2 output blocks (one 64-column phase per tile part), as before (A/B)
   if (p.N == 192 && p.Cout == 64) {
     if (g_opt_exp & 32)
-      return launch_b2<192, 4, 2, 1, true, false, PK_SNAKE, 128, true, 64, false, false, 4, 2>(p, s);
-    return launch_b2<192, 12, 2, 1, true, false, PK_SNAKE, 128, true, 64, false, false, 4, 6>(p, s);
+      return launch_b2<192, 4, 2, 1, true, false, PK_SNAKE, 128, true, 64, false, SP, 4, 2>(p, s);
+    return launch_b2<192, 12, 2, 1, true, false, PK_SNAKE, 128, true, 64, false, SP, 4, 6>(p, s);
   }
   return ST_EINVAL;
 }
+
+int st_bigconv2_ups(const ConvParams& p, hipStream_t s) { return b2_ups<false>(p, s); }
 
 // ---- C = 64 resblock convs (the generator's stage 2 and the 64-channel noise_res) on this engine with 128-frame
 // wave slices (NF = 4): 4-wave blocks (two per CU) of 2 frame slices x 2 output blocks, 256-frame tiles (bit 4; else
@@ -952,16 +940,8 @@ bool st_big64_eligible(const ConvParams& p, int dtype) {
   } else if (!(((g_opt_big64 & 1) && dtype == ST_SPLIT) || ((g_opt_big64 & 2) && dtype == ST_BF16))) {
     return false;
   }
-  if (!(C == 64 || C == 32) || p.Cin != C || p.N != C || p.nchunks * 32 != C) return false;
-  if (!(p.KS == 3 || p.KS == 7 || p.KS == 11) || !(p.dil == 1 || p.dil == 3 || p.dil == 5)) return false;
-  if ((p.kw != 0 && p.kw != p.KS) || p.row_off != 0 || p.stride != 1 || p.up != 1 || p.opad != 0) return false;
-  if (p.pad != p.dil * (p.KS - 1) / 2 || p.Lq != p.Lout || p.Lq != p.Lin) return false;
-  if (p.y_row_off || p.y_f32 || p.epi_tanh || p.epi_lrelu || p.epi_gelu || p.reflect_front || p.zc_period || p.res_shift) return false;
-  if (p.pro.mode != (PRO_AFFINE | PRO_SNAKE) || !p.pro.alpha || !p.pro.stats || !p.pro.gamma) return false;
-  if (p.accb && p.stats) return false;
-  if (p.res ? p.dil != 1 : (p.accb != nullptr)) return false;
-  if (!p.y || p.x_ld % 8 || p.y_ld % 8 || (p.res && p.res_ld % 8) || (p.accb && p.acc_ld % 8)) return false;
-  return true;
+  if (!p.y || !st_resblock_shape(p, 64, 32, 8) || !st_pro_adain_snake(p.pro)) return false;
+  return p.res ? p.dil == 1 : !p.accb;
 }
 
 int st_big64(const ConvParams& p, int dtype, hipStream_t s) {
@@ -995,27 +975,8 @@ int st_bigsplit(const ConvParams& p, hipStream_t s) {
       return launch_b2<64, 4, 2, 1, true, false, PK_SNAKE, 64, true, 32, false, true, 2, 1>(p, s);
     return launch_b2<64, 4, 2, 1, true, false, PK_SNAKE, 64, true, 32, false, true, 2, 2>(p, s);
   }
-  if (st_ups_eligible(p, ST_BF16)) {
-    if (p.N == 2560 && p.Cout == 256)
-      return launch_b2<2560, 8, 2, 1, true, false, PK_SNAKE, 512, true, 256, false, true>(p, s);
-    if (p.N == 640 && p.Cout == 128)
-      return launch_b2<640, 4, 2, 1, true, false, PK_SNAKE, 256, true, 128, false, true>(p, s);
-    if (p.N == 192 && p.Cout == 64) {  // (12-wave blocks as bf16: 1167 -> 926 us; bit 32: the 4-wave blocks)
-      if (g_opt_exp & 32)
-        return launch_b2<192, 4, 2, 1, true, false, PK_SNAKE, 128, true, 64, false, true, 4, 2>(p, s);
-      return launch_b2<192, 12, 2, 1, true, false, PK_SNAKE, 128, true, 64, false, true, 4, 6>(p, s);
-    }
-    return ST_EINVAL;
-  }
-  if (st_front_eligible(p, ST_BF16)) {
-    if (p.Cout == 1024)
-      return p.res ? launch_b2<1024, 8, 3, 1, true, false, PK_LRELU, FE_CINP, false, 1024, false, true>(p, s)
-                   : launch_b2<1024, 8, 3, 1, false, false, PK_LRELU, FE_CINP, false, 1024, false, true>(p, s);
-    if (p.Cout == 512)
-      return p.res ? launch_b2<512, 8, 3, 1, true, false, PK_LRELU, FE_CINP, false, 512, false, true>(p, s)
-                   : launch_b2<512, 8, 3, 1, false, false, PK_LRELU, FE_CINP, false, 512, false, true>(p, s);
-    return ST_EINVAL;
-  }
+  if (st_ups_eligible(p, ST_BF16)) return b2_ups<true>(p, s);
+  if (st_front_eligible(p, ST_BF16)) return b2_front<true>(p, s);
   // resblock convs: 4-wave blocks (two per CU) where the bf16 engine takes them (few tiles, C = 128 k7 / k11)
   const int tm8 = p.Cout == 128 ? 512 : 256;
   const long long tiles8 = (long long)((p.Lq + tm8 - 1) / tm8) * p.B;

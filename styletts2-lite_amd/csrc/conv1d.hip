@@ -23,6 +23,7 @@
 //     fuses bias, residual, 1/sqrt2, the resblock average, tanh, the iSTFTNet reflection pad
 //     and the InstanceNorm statistics; statistics are kept in registers across the tiles of
 //     one utterance and flushed with one fp64 atomic per (utterance, channel, workgroup).
+#include <atomic>
 #include <cstdlib>
 #include <type_traits>
 
@@ -795,8 +796,6 @@ __global__ void __launch_bounds__(64 * WAVES_M * WAVES_N, (kMinWaves<T, MT, SPF>
   }  // tile ranges
 }
 
-int g_num_cu = 0;
-
 template <typename T, typename MT, int WAVES_M, int WAVES_N, int WM, int WN, bool NARROW = false, bool SPF = true>
 int launch_cfg(ConvParams p, hipStream_t stream) {
   using C = ConvCfg<T, MT, WAVES_M, WAVES_N, WM, WN, SPF>;
@@ -841,24 +840,15 @@ int launch_cfg(ConvParams p, hipStream_t stream) {
     ST_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
     attr_set[sg][p.cps - 1] = true;
   }
-  if (!g_num_cu) {
-    int dev = 0;
-    ST_CHECK_HIP(hipGetDevice(&dev));
-    ST_CHECK_HIP(hipDeviceGetAttribute(&g_num_cu, hipDeviceAttributeMultiprocessorCount, dev));
-  }
-  int per_cu = occupancy_cached((const void*)kern, C::NT, lds);
-  if (per_cu < 1) per_cu = 1;
   const long long ntn = (p.N + C::BN - 1) / C::BN, ntm = (p.Lq + C::BM - 1) / C::BM;
   const long long tiles = ntn * ntm * p.B;
   if (tiles <= 0) return ST_OK;
   if (tiles > 0x7fffffffLL) return ST_EINVAL;
+  StGrid g;  // (g.seg > 0 only where sg is set: st_seg_choice's conditions but for the grid size)
+  ST_CHECK(st_grid(p, tiles, occupancy_cached((const void*)kern, C::NT, lds), false, &g));
   ConvParams q = p;
-  q.seg = sg ? st_seg_choice(p, 1, g_num_cu * per_cu) : 0;
-  const long long nvb = q.seg ? (long long)p.B * q.seg : tiles;
-  long long grid = (long long)g_num_cu * per_cu;
-  if (grid > nvb) grid = nvb;
-  if (g_opt_grid_cap > 0 && grid > g_opt_grid_cap) grid = g_opt_grid_cap;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(C::NT), lds, stream, q);
+  q.seg = g.seg;
+  hipLaunchKernelGGL(kern, dim3(g.grid), dim3(C::NT), lds, stream, q);
   return (int)hipGetLastError();
 }
 
@@ -883,7 +873,8 @@ int launch_typed(const ConvParams& p, hipStream_t stream) {
     // few tiles (small batches: the 400-frame front-end at B = 1 makes 16 tiles of 256 x 128 for 256
     // CUs): BM 64 x BN 128 tiles, 4x the workgroups
     const long long big = (long long)((p.N + 127) / 128) * ((p.Lq + 255) / 256) * p.B;
-    const int ncu = g_num_cu ? g_num_cu : 256;
+    int ncu = 256;  // (stands when there is no device to ask)
+    (void)st_num_cu(&ncu);
     if (big < ncu / 2) return launch_cfg<T, MT, 2, 2, 1, 2, false, SPF>(p, stream);
   }
   if (p.N <= 32) return launch_cfg<T, MT, 4, 1, 2, 1, false, SPF>(p, stream);     // BM 256 x BN 32, 4 waves
@@ -912,22 +903,98 @@ int st_seg_choice(const ConvParams& p, int upu, int gmax) {
   return seg >= 1 ? seg : 0;
 }
 
+int st_num_cu(int* ncu) {
+  static std::atomic<int> cached{0};
+  int n = cached.load(std::memory_order_relaxed);
+  if (!n) {
+    int dev = 0;
+    ST_CHECK_HIP(hipGetDevice(&dev));
+    ST_CHECK_HIP(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
+    cached.store(n, std::memory_order_relaxed);
+  }
+  *ncu = n;
+  return ST_OK;
+}
+
+int st_grid(const ConvParams& p, long long tiles, int per_cu, bool collapse, StGrid* g) {
+  int ncu = 0;
+  ST_CHECK(st_num_cu(&ncu));
+  const int gmax = ncu * (per_cu < 1 ? 1 : per_cu);
+  const int seg = st_seg_choice(p, 1, gmax);
+  const long long nvb = seg ? (long long)p.B * seg : tiles;
+  long long grid = gmax < nvb ? gmax : nvb;
+  if (g_opt_grid_cap > 0 && grid > g_opt_grid_cap) grid = g_opt_grid_cap;
+  g->segk = seg > 0 && !(collapse && grid == nvb);
+  g->seg = g->segk ? seg : 0;
+  g->grid = (unsigned)grid;
+  return ST_OK;
+}
+
+bool st_resblock_shape(const ConvParams& p, int c0, int c1, int align) {
+  const int C = p.Cout;
+  if (!(C == c0 || C == c1) || p.Cin != C || p.N != C || p.nchunks * 32 != C) return false;
+  if (!(p.KS == 3 || p.KS == 7 || p.KS == 11) || !(p.dil == 1 || p.dil == 3 || p.dil == 5)) return false;
+  if ((p.kw != 0 && p.kw != p.KS) || p.row_off != 0 || p.stride != 1 || p.up != 1 || p.opad != 0) return false;
+  if (p.pad != p.dil * (p.KS - 1) / 2 || p.Lq != p.Lout || p.Lq != p.Lin) return false;
+  if (p.y_row_off || p.y_f32 || p.epi_tanh || p.epi_lrelu || p.epi_gelu || p.reflect_front || p.zc_period || p.res_shift) return false;
+  if (p.accb && p.stats) return false;  // the running-sum launch keeps no statistics
+  return !(p.x_ld % align || p.y_ld % align || (p.res && p.res_ld % align) || (p.accb && p.acc_ld % align));
+}
+
+bool st_polyphase_shape(const ConvParams& p) {
+  return p.res && !p.accb && p.KS == 2 && (p.kw == 0 || p.kw == 2) && p.dil == 1 && p.stride == 1 && p.pad == 1 &&
+         p.row_off == 0 && p.pro.mode == PRO_SNAKE && p.pro.alpha && p.res_shift == 0 && p.y_row_off == 0 &&
+         !p.reflect_front && !p.epi_tanh && !p.epi_lrelu && !p.epi_gelu && !p.y_f32 && p.zc_period == 0 &&
+         p.x_ld % 8 == 0 && p.y_ld % 8 == 0 && p.res_ld % 8 == 0;
+}
+
 unsigned long long* g_dbg_stamps = nullptr;  // stts_set_debug_buffer
+
+// The route list: the first step whose rule admits the launch serves it.  st_conv1d_engine reports a step's engine and
+// st_conv1d runs it from this one table, so the engine reported (profiles, the training conv's frame format in
+// convbwd.hip) is the engine launched.  No step: the general engine.
+namespace {
+
+struct Route {
+  bool (*ok)(const ConvParams&, int dtype);
+  int (*run)(const ConvParams&, int dtype, hipStream_t);
+  int engine;
+  int engine_split;  // the engine reported for ST_SPLIT
+};
+template <int (*F)(const ConvParams&, hipStream_t)>
+int run_of(const ConvParams& p, int, hipStream_t s) { return F(p, s); }
+
+const Route kRoutes[] = {
+    {[](const ConvParams& p, int) { return g_opt_head && st_head_eligible(p); }, st_head, ST_ENGINE_HEAD, ST_ENGINE_HEAD},
+    {st_front_eligible, run_of<st_bigconv2_front>, ST_ENGINE_BIGCONV, ST_ENGINE_BIGCONV},
+    {st_ups_eligible, run_of<st_bigconv2_ups>, ST_ENGINE_BIGCONV, ST_ENGINE_BIGCONV},
+    {st_resconv_ups_eligible, run_of<st_resconv_ups>, ST_ENGINE_RESCONV, ST_ENGINE_RESCONV},
+    {st_big64_eligible, st_big64, ST_ENGINE_BIGCONV, ST_ENGINE_BIGSPLIT},
+    {[](const ConvParams& p, int dt) { return g_opt_resconv && st_resconv_eligible(p, dt); }, run_of<st_resconv>,
+     ST_ENGINE_RESCONV, ST_ENGINE_RESCONV},
+    {[](const ConvParams& p, int dt) { return g_opt_resconv && st_bigconv_eligible(p, dt); }, run_of<st_bigconv>,
+     ST_ENGINE_BIGCONV, ST_ENGINE_BIGCONV},
+    {st_pw_split_eligible, run_of<st_pw_split>, ST_ENGINE_PW, ST_ENGINE_PW},
+    {st_pw_eligible, run_of<st_pw>, ST_ENGINE_PW, ST_ENGINE_PW},
+    {st_ressplit_eligible, run_of<st_ressplit>, ST_ENGINE_RESSPLIT, ST_ENGINE_RESSPLIT},
+    {st_bigsplit_eligible, run_of<st_bigsplit>, ST_ENGINE_BIGSPLIT, ST_ENGINE_BIGSPLIT},
+};
+
+// (q.kw is set).  The time-expanded MSD input runs on the general engine only
+const Route* conv_route(const ConvParams& q, int dtype) {
+  if (q.tx_H) return nullptr;
+  for (const Route& r : kRoutes)
+    if (r.ok(q, dtype)) return &r;
+  return nullptr;
+}
+
+}  // namespace
 
 int st_conv1d_engine(const ConvParams& p, int dtype) {
   ConvParams q = p;
   if (q.kw <= 0) q.kw = q.KS;
-  if (q.tx_H) return ST_ENGINE_IGEMM;
-  if (g_opt_head && st_head_eligible(q)) return ST_ENGINE_HEAD;
-  if (st_front_eligible(q, dtype) || st_ups_eligible(q, dtype)) return ST_ENGINE_BIGCONV;
-  if (st_resconv_ups_eligible(q, dtype)) return ST_ENGINE_RESCONV;
-  if (st_big64_eligible(q, dtype)) return dtype == ST_SPLIT ? ST_ENGINE_BIGSPLIT : ST_ENGINE_BIGCONV;
-  if (g_opt_resconv && st_resconv_eligible(q, dtype)) return ST_ENGINE_RESCONV;
-  if (g_opt_resconv && st_bigconv_eligible(q, dtype)) return ST_ENGINE_BIGCONV;
-  if (st_pw_split_eligible(q, dtype) || st_pw_eligible(q, dtype)) return ST_ENGINE_PW;
-  if (st_ressplit_eligible(q, dtype)) return ST_ENGINE_RESSPLIT;
-  if (st_bigsplit_eligible(q, dtype)) return ST_ENGINE_BIGSPLIT;
-  return ST_ENGINE_IGEMM;
+  const Route* r = conv_route(q, dtype);
+  return !r ? ST_ENGINE_IGEMM : dtype == ST_SPLIT ? r->engine_split : r->engine;
 }
 
 int st_conv1d(const ConvParams& p, int dtype, hipStream_t stream) {
@@ -938,29 +1005,11 @@ int st_conv1d(const ConvParams& p, int dtype, hipStream_t stream) {
   if (q.kw <= 0) q.kw = q.KS;
   q.dbg = g_opt_debug;
   q.stamps = g_dbg_stamps;
-  if (q.tx_H) {  // the time-expanded MSD input: general engine only (chunk dh = one 32-channel chunk)
-    if (q.tx_H < 1 || q.nchunks != 3 || q.Cin != 96 || q.x_ld != 32 || q.B % q.tx_H) return ST_EINVAL;
-    if (dtype == ST_FP32) return launch_typed<float, float>(q, stream);
-    if (dtype == ST_BF16) return launch_typed<bf16_t, bf16_t>(q, stream);
-    if (dtype == ST_SPLIT) return launch_typed<float, bf16_t, true>(q, stream);
-    if (dtype == ST_BF16F) return launch_typed<float, bf16_t, false>(q, stream);
-    return ST_EDTYPE;
-  }
-  if (g_opt_head && st_head_eligible(q)) return st_head(q, dtype, stream);
-  if (st_front_eligible(q, dtype)) return st_bigconv2_front(q, stream);
-  if (st_ups_eligible(q, dtype)) return st_bigconv2_ups(q, stream);
-  if (st_resconv_ups_eligible(q, dtype)) return st_resconv_ups(q, stream);
-  if (st_big64_eligible(q, dtype)) return st_big64(q, dtype, stream);
-  if (g_opt_resconv && st_resconv_eligible(q, dtype)) return st_resconv(q, stream);
-  if (g_opt_resconv && st_bigconv_eligible(q, dtype)) return st_bigconv(q, stream);
-  if (st_pw_split_eligible(q, dtype)) return st_pw_split(q, stream);
-  if (st_pw_eligible(q, dtype)) return st_pw(q, stream);
-  if (st_ressplit_eligible(q, dtype)) return st_ressplit(q, stream);
-  if (st_bigsplit_eligible(q, dtype)) return st_bigsplit(q, stream);
+  // the time-expanded MSD input (chunk dh = one 32-channel chunk)
+  if (q.tx_H && (q.tx_H < 1 || q.nchunks != 3 || q.Cin != 96 || q.x_ld != 32 || q.B % q.tx_H)) return ST_EINVAL;
+  if (const Route* r = conv_route(q, dtype)) return r->run(q, dtype, stream);
   if (dtype == ST_FP32) return launch_typed<float, float>(q, stream);
-  if (dtype == ST_BF16) {
-    return launch_typed<bf16_t, bf16_t>(q, stream);
-  }
+  if (dtype == ST_BF16) return launch_typed<bf16_t, bf16_t>(q, stream);
   if (dtype == ST_SPLIT) return launch_typed<float, bf16_t, true>(q, stream);
   if (dtype == ST_BF16F) return launch_typed<float, bf16_t, false>(q, stream);
   return ST_EDTYPE;

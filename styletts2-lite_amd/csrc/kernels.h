@@ -92,6 +92,28 @@ __device__ __forceinline__ void tile_range(const ConvParams& p, int v, int nv, l
 // Segmented when B is a multiple of 32 (every config-4 shard, 256 / W utterances): seg = gmax / (32 upu), so B = 32 k
 // gives every workgroup k ranges of equal size; 0 (the even split) otherwise, or with STTS_OPT_SEGPART 0
 int st_seg_choice(const ConvParams& p, int upu, int gmax);
+// host: the device's CU count, queried once per process; returns the hipError_t.  On failure nothing is cached and
+// *ncu is left as it was: predicates that must answer without a device preset their own answer (256) or decline
+int st_num_cu(int* ncu);
+// host: the grid of a persistent conv launch over `tiles` tiles with up to per_cu workgroups per CU: the segment
+// choice, min(CUs per_cu, B seg or tiles), then STTS_OPT_GRID_CAP.  seg goes into ConvParams::seg.  collapse: a launch
+// with one segment per workgroup is the even split of the plain kernel (every utterance has the same tile count), so
+// seg = 0 and segk = false then; segk picks the SEG instantiation of a plain / segmented kernel pair
+struct StGrid {
+  unsigned grid;
+  int seg;
+  bool segk;
+};
+int st_grid(const ConvParams& p, long long tiles, int per_cu, bool collapse, StGrid* g);
+// host: what the resblock engines' eligibility rules share: a C -> C 'same' conv with C = c0 or c1, K in {3, 7, 11},
+// dil in {1, 3, 5}, no 2-D taps, stride, upsampling or epilogue extras, no statistics of a running-sum launch, rows
+// aligned to `align` elements.  Dtype, prologue and the engine's own conditions stay with each st_*_eligible
+bool st_resblock_shape(const ConvParams& p, int c0, int c1, int align);
+inline bool st_pro_adain_snake(const Prologue& pro) {
+  return pro.mode == (PRO_AFFINE | PRO_SNAKE) && pro.alpha && pro.stats && pro.gamma;
+}
+// host: the same for the 2-tap polyphase upsamplers (Snake prologue, noise-branch residual, 8-element rows)
+bool st_polyphase_shape(const ConvParams& p);
 
 int st_conv1d(const ConvParams& p, int dtype, hipStream_t stream);
 // slot base of workgroup `g` (see ConvParams::stats_slots)

@@ -444,22 +444,14 @@ bool st_pw_eligible(const ConvParams& p, int dtype) {
   return true;
 }
 
-int g_num_cu_pw = 0;
-
 int st_pw(const ConvParams& p, hipStream_t stream) {
   const int ntm = (p.Lq + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
   const long long tiles = (long long)ntm * ntn * p.B;
   if (tiles <= 0) return ST_OK;
-  if (!g_num_cu_pw) {
-    int dev = 0;
-    ST_CHECK_HIP(hipGetDevice(&dev));
-    ST_CHECK_HIP(hipDeviceGetAttribute(&g_num_cu_pw, hipDeviceAttributeMultiprocessorCount, dev));
-  }
+  StGrid g;
+  ST_CHECK(st_grid(p, tiles, 2, false, &g));  // 220-238 VGPRs: two 4-wave blocks per CU
   ConvParams q = p;
-  q.seg = st_seg_choice(p, 1, g_num_cu_pw * 2);
-  long long blocks = (long long)g_num_cu_pw * 2;  // 220-238 VGPRs: two 4-wave blocks per CU
-  if (blocks > (q.seg ? (long long)p.B * q.seg : tiles)) blocks = q.seg ? (long long)p.B * q.seg : tiles;
-  if (g_opt_grid_cap > 0 && blocks > g_opt_grid_cap) blocks = g_opt_grid_cap;
+  q.seg = g.seg;
   const size_t lds = p.pro.mode ? (size_t)p.nchunks * 32 * 4 * sizeof(float) : 0;
   static bool attr = false;
   if (!attr) {  // static ring (<= 62 KB) + the coefficient table can exceed the 64 KB default
@@ -469,9 +461,9 @@ int st_pw(const ConvParams& p, hipStream_t stream) {
   }
   if (lds > 96 * 1024) return ST_EINVAL;
   if (p.KS == 1)
-    hipLaunchKernelGGL(k_pwgemm<1>, dim3((unsigned)blocks), dim3(NT), lds, stream, q, ntm, ntn);
+    hipLaunchKernelGGL(k_pwgemm<1>, dim3(g.grid), dim3(NT), lds, stream, q, ntm, ntn);
   else
-    hipLaunchKernelGGL(k_pwgemm<2>, dim3((unsigned)blocks), dim3(NT), lds, stream, q, ntm, ntn);
+    hipLaunchKernelGGL(k_pwgemm<2>, dim3(g.grid), dim3(NT), lds, stream, q, ntm, ntn);
   return (int)hipGetLastError();
 }
 
@@ -484,21 +476,19 @@ bool st_pw_split_eligible(const ConvParams& p, int dtype) {
   if (p.accb || p.y_f32 || p.y_row_off || p.epi_tanh || p.epi_lrelu || p.reflect_front || p.zc_period) return false;
   if (p.pro.mode & ~(PRO_AFFINE | PRO_SNAKE | PRO_LRELU)) return false;
   if (p.x_ld % 8 || p.y_ld % 8) return false;
-  if (!g_num_cu_pw) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&g_num_cu_pw, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-      return false;
-  }
+  int ncu = 0;
+  if (st_num_cu(&ncu)) return false;
   const long long tiles = (long long)((p.Lq + BM - 1) / BM) * ((p.N + BN - 1) / BN) * p.B;
-  return tiles < g_num_cu_pw / 2 && p.nchunks >= 8;  // small launches with a long K only
+  return tiles < ncu / 2 && p.nchunks >= 8;  // small launches with a long K only
 }
 
 int st_pw_split(const ConvParams& p, hipStream_t stream) {
   const int ntm = (p.Lq + BM - 1) / BM, ntn = (p.N + BN - 1) / BN;
   const long long tiles = (long long)ntm * ntn * p.B;
   // slices: about two blocks per CU, at least 4 chunks each, and the partials must fit the workspace
-  int S = (int)((2LL * g_num_cu_pw + tiles - 1) / tiles);
+  int ncu = 0;
+  ST_CHECK(st_num_cu(&ncu));
+  int S = (int)((2LL * ncu + tiles - 1) / tiles);
   S = S < 1 ? 1 : S;
   if (S > p.nchunks / 4) S = p.nchunks / 4;
   while (S > 1 && (long long)S * p.B * p.Lq * p.N > p.splitk_ws_elems) --S;

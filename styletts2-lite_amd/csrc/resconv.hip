@@ -541,8 +541,6 @@ __global__ void __launch_bounds__(64 * WAVES, MINB ? MINB : 8 / WAVES) k_resconv
   }
 }
 
-int g_num_cu_rc = 0;
-
 // block shape: 4 x 1 waves at C = 32, 8 x 2 at C = 64
 template <int C, int K, int DIL, bool ACC, bool UPS = false, bool IL = false, int MINB = 0>
 int launch_rc(const ConvParams& p, hipStream_t stream) {
@@ -557,22 +555,12 @@ int launch_rc(const ConvParams& p, hipStream_t stream) {
     ST_CHECK_HIP(hipFuncSetAttribute((const void*)kern1, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
     attr = true;
   }
-  if (!g_num_cu_rc) {
-    int dev = 0;
-    ST_CHECK_HIP(hipGetDevice(&dev));
-    ST_CHECK_HIP(hipDeviceGetAttribute(&g_num_cu_rc, hipDeviceAttributeMultiprocessorCount, dev));
-  }
-  int per_cu = occupancy_cached((const void*)kern0, G::NT, G::LDS);
-  if (per_cu < 1) per_cu = 1;
   const long long tiles = (long long)((p.Lq + G::BM - 1) / G::BM) * p.B;
+  StGrid g;
+  ST_CHECK(st_grid(p, tiles, occupancy_cached((const void*)kern0, G::NT, G::LDS), true, &g));
   ConvParams q = p;
-  const int seg = st_seg_choice(p, 1, g_num_cu_rc * per_cu);
-  long long grid = (long long)g_num_cu_rc * per_cu;
-  if (grid > (seg ? (long long)p.B * seg : tiles)) grid = seg ? (long long)p.B * seg : tiles;
-  if (g_opt_grid_cap > 0 && grid > g_opt_grid_cap) grid = g_opt_grid_cap;
-  const bool segk = seg > 0 && grid < (long long)p.B * seg;  // (one segment per workgroup = the plain even split)
-  q.seg = segk ? seg : 0;
-  hipLaunchKernelGGL(segk ? kern1 : kern0, dim3((unsigned)grid), dim3(G::NT), G::LDS, stream, q);
+  q.seg = g.seg;
+  hipLaunchKernelGGL(g.segk ? kern1 : kern0, dim3(g.grid), dim3(G::NT), G::LDS, stream, q);
   return (int)hipGetLastError();
 }
 
@@ -892,8 +880,6 @@ __global__ void __launch_bounds__(512, 1) k_resconv_pp(const ConvParams p) {
   }  // tile ranges
 }
 
-int g_num_cu_pp = 0;
-
 template <int K, int DIL, bool ACC>
 int launch_pp(const ConvParams& p, hipStream_t stream) {
   using G = PP<K, DIL>;
@@ -903,18 +889,12 @@ int launch_pp(const ConvParams& p, hipStream_t stream) {
     ST_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
     attr = true;
   }
-  if (!g_num_cu_pp) {
-    int dev = 0;
-    ST_CHECK_HIP(hipGetDevice(&dev));
-    ST_CHECK_HIP(hipDeviceGetAttribute(&g_num_cu_pp, hipDeviceAttributeMultiprocessorCount, dev));
-  }
   const long long tiles = (long long)((p.Lq + G::BM - 1) / G::BM) * p.B;
+  StGrid g;
+  ST_CHECK(st_grid(p, tiles, 1, false, &g));
   ConvParams q = p;
-  q.seg = st_seg_choice(p, 1, g_num_cu_pp);
-  long long grid = g_num_cu_pp;
-  if (grid > (q.seg ? (long long)p.B * q.seg : tiles)) grid = q.seg ? (long long)p.B * q.seg : tiles;
-  if (g_opt_grid_cap > 0 && grid > g_opt_grid_cap) grid = g_opt_grid_cap;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(G::NT), G::LDS, stream, q);
+  q.seg = g.seg;
+  hipLaunchKernelGGL(kern, dim3(g.grid), dim3(G::NT), G::LDS, stream, q);
   return (int)hipGetLastError();
 }
 
@@ -963,19 +943,9 @@ int launch_rc_k(const ConvParams& p, hipStream_t s) {
 }  // namespace
 
 bool st_resconv_eligible(const ConvParams& p, int dtype) {
-  if (dtype != ST_BF16) return false;
-  const int C = p.Cout;
-  if (!(C == 32 || C == 64) || p.Cin != C || p.N != C || p.nchunks * 32 != C) return false;
-  if (!(p.KS == 3 || p.KS == 7 || p.KS == 11) || !(p.dil == 1 || p.dil == 3 || p.dil == 5)) return false;
-  if ((p.kw != 0 && p.kw != p.KS) || p.row_off != 0 || p.stride != 1 || p.up != 1 || p.opad != 0) return false;
-  if (p.pad != p.dil * (p.KS - 1) / 2 || p.Lq != p.Lout || p.Lq != p.Lin) return false;
-  if (p.y_row_off || p.y_f32 || p.epi_tanh || p.epi_lrelu || p.epi_gelu || p.reflect_front || p.zc_period || p.res_shift) return false;
+  if (dtype != ST_BF16 || !st_resblock_shape(p, 32, 64, 8)) return false;
   // AdaIN -> Snake (the decoder), or no prologue (the training step's convs, STTS_OPT_PLAINRC)
-  const bool snake = p.pro.mode == (PRO_AFFINE | PRO_SNAKE) && p.pro.alpha && p.pro.stats && p.pro.gamma;
-  if (!snake && !(p.pro.mode == 0 && g_opt_plainrc)) return false;
-  if (p.accb && p.stats) return false;  // the running-sum launch keeps no statistics
-  if (p.x_ld % 8 || p.y_ld % 8 || (p.res && p.res_ld % 8) || (p.accb && p.acc_ld % 8)) return false;
-  return true;
+  return st_pro_adain_snake(p.pro) || (p.pro.mode == 0 && g_opt_plainrc);
 }
 
 int st_resconv(const ConvParams& p, hipStream_t stream) {
@@ -986,11 +956,8 @@ int st_resconv(const ConvParams& p, hipStream_t stream) {
 
 // HiFi-GAN ups[3] (64 -> 32 channels, x2) on this engine (STTS_OPT_UPS with ups[0] / ups[1] on bigconv2)
 bool st_resconv_ups_eligible(const ConvParams& p, int dtype) {
-  if (!g_opt_ups || dtype != ST_BF16 || p.up != 2 || !p.res || p.accb) return false;
-  return p.Cin == 64 && p.N == 64 && p.Cout == 32 && p.nchunks == 2 && p.KS == 2 && (p.kw == 0 || p.kw == 2) &&
-         p.dil == 1 && p.stride == 1 && p.pad == 1 && p.row_off == 0 && p.pro.mode == PRO_SNAKE && p.pro.alpha &&
-         p.res_shift == 0 && p.y_row_off == 0 && !p.reflect_front && !p.epi_tanh && !p.epi_lrelu && !p.epi_gelu &&
-         !p.y_f32 && p.zc_period == 0 && p.x_ld % 8 == 0 && p.y_ld % 8 == 0 && p.res_ld % 8 == 0;
+  if (!g_opt_ups || dtype != ST_BF16 || p.up != 2) return false;
+  return p.Cin == 64 && p.N == 64 && p.Cout == 32 && p.nchunks == 2 && st_polyphase_shape(p);
 }
 
 int st_resconv_ups(const ConvParams& p, hipStream_t stream) {

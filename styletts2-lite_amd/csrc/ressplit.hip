@@ -361,8 +361,6 @@ __global__ void __launch_bounds__(NOUT == 32 ? 256 : 512, NOUT == 32 ? 2 : 1) k_
   }  // tile ranges
 }
 
-int g_num_cu_rs = 0;
-
 template <int NOUT, int K, int DIL, int PASS, bool ACC, bool PF = false>
 int launch_rs_pf(const ConvParams& p, hipStream_t stream) {
   using G = RS<NOUT, K, DIL>;
@@ -374,22 +372,12 @@ int launch_rs_pf(const ConvParams& p, hipStream_t stream) {
     ST_CHECK_HIP(hipFuncSetAttribute((const void*)kern1, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS));
     attr = true;
   }
-  if (!g_num_cu_rs) {
-    int dev = 0;
-    ST_CHECK_HIP(hipGetDevice(&dev));
-    ST_CHECK_HIP(hipDeviceGetAttribute(&g_num_cu_rs, hipDeviceAttributeMultiprocessorCount, dev));
-  }
-  int per_cu = occupancy_cached((const void*)kern0, G::NT, G::LDS);
-  if (per_cu < 1) per_cu = 1;
   const long long tiles = (long long)((p.Lq + G::BM - 1) / G::BM) * p.B;
+  StGrid g;
+  ST_CHECK(st_grid(p, tiles, occupancy_cached((const void*)kern0, G::NT, G::LDS), true, &g));
   ConvParams q = p;
-  const int seg = st_seg_choice(p, 1, g_num_cu_rs * per_cu);
-  long long grid = (long long)g_num_cu_rs * per_cu;
-  if (grid > (seg ? (long long)p.B * seg : tiles)) grid = seg ? (long long)p.B * seg : tiles;
-  if (g_opt_grid_cap > 0 && grid > g_opt_grid_cap) grid = g_opt_grid_cap;
-  const bool segk = seg > 0 && grid < (long long)p.B * seg;  // (one segment per workgroup = the plain even split)
-  q.seg = segk ? seg : 0;
-  hipLaunchKernelGGL(segk ? kern1 : kern0, dim3((unsigned)grid), dim3(G::NT), G::LDS, stream, q);
+  q.seg = g.seg;
+  hipLaunchKernelGGL(g.segk ? kern1 : kern0, dim3(g.grid), dim3(G::NT), G::LDS, stream, q);
   return (int)hipGetLastError();
 }
 
@@ -431,19 +419,10 @@ int launch_rs_k(const ConvParams& p, hipStream_t s) {
 }  // namespace
 
 bool st_ressplit_eligible(const ConvParams& p, int dtype) {
-  if (!g_opt_ressplit || dtype != ST_SPLIT) return false;
-  const int C = p.Cout;
-  if (!(C == 32 || C == 64) || p.Cin != C || p.N != C || p.nchunks * 32 != C) return false;
-  if (!(p.KS == 3 || p.KS == 7 || p.KS == 11) || !(p.dil == 1 || p.dil == 3 || p.dil == 5)) return false;
-  if ((p.kw != 0 && p.kw != p.KS) || p.row_off != 0 || p.stride != 1 || p.up != 1 || p.opad != 0) return false;
-  if (p.pad != p.dil * (p.KS - 1) / 2 || p.Lq != p.Lout || p.Lq != p.Lin) return false;
-  if (p.y_row_off || p.y_f32 || p.epi_tanh || p.epi_lrelu || p.epi_gelu || p.reflect_front || p.zc_period || p.res_shift) return false;
-  if (p.pro.mode != (PRO_AFFINE | PRO_SNAKE) || !p.pro.alpha || !p.pro.stats || !p.pro.gamma) return false;
-  if (p.accb && p.stats) return false;
-  if (!p.y || p.x_ld % 4 || p.y_ld % 4 || (p.res && p.res_ld % 4) || (p.accb && p.acc_ld % 4)) return false;
+  if (!g_opt_ressplit || dtype != ST_SPLIT || !p.y) return false;
+  if (!st_resblock_shape(p, 32, 64, 4) || !st_pro_adain_snake(p.pro)) return false;
   // C = 64 runs in two passes through the fp32 partial scratch
-  if (C == 64 && (!p.splitk_ws || p.splitk_ws_elems < (long long)p.B * p.Lq * 64)) return false;
-  return true;
+  return p.Cout == 32 || (p.splitk_ws && p.splitk_ws_elems >= (long long)p.B * p.Lq * 64);
 }
 
 int st_ressplit(const ConvParams& p, hipStream_t stream) {
