@@ -5,7 +5,7 @@ read side by side.  engine.lib() applies the whole table when it loads the libra
 it to the headers (names both ways, argument count, the class of every argument and of the return value).  A new
 entry point gets its line here and nowhere else.
 
-Every pointer is a c_void_p (tensors go through engine._ptr) except the host int / double arrays and out-pointers
+Every pointer is a c_void_p (engine.call passes a tensor there as its data_ptr()) except the host int / double arrays and out-pointers
 that callers pass as ctypes arrays or byref(), and the two string returns.
 """
 import ctypes

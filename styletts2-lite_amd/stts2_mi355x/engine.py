@@ -52,7 +52,7 @@ def lib():
     _LIB = L
     if os.environ.get("STTS_OPTS"):
         for k, v in OPT_DEFAULTS.items():
-            check(L.stts_set_option(int(k), int(v)), "stts_set_option")
+            call("stts_set_option", int(k), int(v))
     return L
 
 
@@ -74,7 +74,7 @@ for _kv in filter(None, os.environ.get("STTS_OPTS", "").split(",")):
 
 def set_option(key: int, value: int) -> None:
     """Process-wide engine option (include/stts2.h STTS_OPT_*)."""
-    check(lib().stts_set_option(int(key), int(value)), "stts_set_option")
+    call("stts_set_option", int(key), int(value))
 
 
 def get_option(key: int) -> int:
@@ -127,13 +127,90 @@ _GET_DEVICE = getattr(torch._C, "_cuda_getDevice", None)
 
 
 def _stream():
+    """The current HIP stream's handle as an int (the entry points' argtypes make it the hipStream_t)."""
     if _RAW_STREAM is not None and _GET_DEVICE is not None:
-        return ctypes.c_void_p(_RAW_STREAM(_GET_DEVICE()))
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+        return _RAW_STREAM(_GET_DEVICE())
+    return torch.cuda.current_stream().cuda_stream  # (a torch without the raw query)
 
 
 def _ptr(t):
+    """A tensor (or None) as a c_void_p: for the tests and tools that call lib() directly; the package uses call()."""
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+
+
+def query(name, *args):
+    """A size query (*_workspace_bytes, *_out_elems, *_scratch_bytes, ...: they return long long and take no stream):
+    its value; a negative one is the query's STTS_E* code for these arguments and raises.  Needs no device."""
+    n = int(getattr(lib(), name)(*args))
+    if n < 0:
+        check(n, name)
+    return n
+
+
+def _workspace(query_name: str, device, *args):
+    """(buffer, bytes) for a kernel whose size query is query(query_name, *args): for call sites that share one
+    buffer between calls or pass it elsewhere than right before the stream; the others say call(..., ws=(...))."""
+    nbytes = query(query_name, *args)
+    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=device), nbytes
+
+
+_ENTRIES = {}  # name -> _bind(name), built on the entry point's first call
+
+
+def _bind(name, fn=None):
+    """run(args, ws) for one status-returning entry point, built once from its abi.SIGNATURES row (`fn` replaces the
+    library's function: tests).  A tensor at a c_void_p position goes as its data_ptr(); None stays None, ctypes' NULL;
+    anything else (model handles, ctypes arrays, byref(), ints, floats) is left to argtypes.  One argument fewer than
+    the signature: the current stream is appended.  ws = (query name, *query args): the workspace is sized by that
+    query, allocated on the device of the first tensor argument and passed as (buffer, bytes) right before the
+    stream.  Any other argument count raises before anything is launched; a non-zero status raises as check()."""
+    argtypes, restype = SIGNATURES[name]
+    if restype is not c_int:
+        raise TypeError(f"{name} returns no status: query() serves the size queries")
+    n = len(argtypes)
+    ptrs = tuple(i for i, t in enumerate(argtypes) if t is c_vp)
+    ends_in_ptr = n > 0 and argtypes[-1] is c_vp  # where a stream can be
+    takes_ws = list(argtypes[-3:]) == [c_vp, c_ll, c_vp]
+    cache = fn is None
+    if cache:
+        fn = getattr(lib(), name)
+    Tensor = torch.Tensor
+
+    def run(args, ws=None):
+        given = len(args)
+        if ws is not None:
+            if not takes_ws:
+                raise TypeError(f"{name} does not end in (workspace, bytes, stream): pass the workspace explicitly")
+            if given != n - 3:
+                raise TypeError(f"{name} takes {n} arguments, got {given} + workspace, bytes and stream (ws=)")
+            dev = next((args[i].device for i in ptrs[:-2] if isinstance(args[i], Tensor)), None)
+            if dev is None:
+                raise TypeError(f"{name}: ws= puts the workspace on the first tensor argument's device; there is none")
+            a = [*args, *_workspace(ws[0], dev, *ws[1:]), _stream()]
+        elif given == n:
+            a = list(args)
+        elif given == n - 1 and ends_in_ptr:
+            a = [*args, _stream()]
+        else:
+            raise TypeError(f"{name} takes {n} arguments" + (" (the stream may be left out)" if ends_in_ptr else "")
+                            + f", got {given}")
+        for i in ptrs:
+            v = a[i]
+            if isinstance(v, Tensor):
+                a[i] = v.data_ptr()
+        rc = fn(*a)
+        if rc != 0:
+            check(rc, name)
+
+    if cache:
+        _ENTRIES[name] = run
+    return run
+
+
+def call(name, *args, ws=None):
+    """Call the entry point `name` of the library (see _bind): call("stts_snake_bwd", xc, ac, dyc, B, L, C, dx, da,
+    ws=("stts_snake_workspace_bytes", B, L, C)).  A new entry point needs its abi.SIGNATURES row and nothing else."""
+    (_ENTRIES.get(name) or _bind(name))(args, ws)
 
 
 def _dev_f32(t, device):
@@ -151,7 +228,7 @@ class NativeModel:
         self.kind = kind
         arr = (c_int * len(cfg))(*[int(v) for v in cfg])
         h = c_vp()
-        check(L.stts_model_create(kind, arr, len(cfg), ctypes.byref(h)), "stts_model_create")
+        call("stts_model_create", kind, arr, len(cfg), ctypes.byref(h))
         self.h = h
         self.device = torch.device("cuda", torch.cuda.current_device())
         sd = module.state_dict(keep_vars=True)
@@ -171,31 +248,25 @@ class NativeModel:
                 raise ValueError(f"{name}: numel {t.numel()} != plan {L.stts_param_numel(h, i)}")
             self._keep.append(t)
             self.names.append(name)
-            check(L.stts_set_param(h, i, _ptr(t)), "stts_set_param")
+            call("stts_set_param", h, i, t)
         self._packed = {}
         self._ws = {}
 
     def pack(self, dtype: str):
         if dtype not in self._packed:
-            L = lib()
             dt = DTYPES[dtype]
-            nb = L.stts_packed_bytes(self.h, dt)
-            if nb < 0:
-                check(int(nb), "stts_packed_bytes")
-            buf = torch.empty(max(int(nb), 1), dtype=torch.uint8, device=self.device)
-            check(L.stts_pack(self.h, dt, _ptr(buf), int(nb), _stream()), "stts_pack")
+            nb = query("stts_packed_bytes", self.h, dt)
+            buf = torch.empty(max(nb, 1), dtype=torch.uint8, device=self.device)
+            call("stts_pack", self.h, dt, buf, nb)
             self._packed[dtype] = buf
         return self._packed[dtype]
 
     def workspace(self, dtype: str, B: int, T: int):
-        L = lib()
-        nb = L.stts_workspace_bytes(self.h, DTYPES[dtype], int(B), int(T))
-        if nb < 0:
-            check(int(nb), "stts_workspace_bytes")
+        nb = query("stts_workspace_bytes", self.h, DTYPES[dtype], int(B), int(T))
         cur = self._ws.get(dtype)
         if cur is None or cur.numel() < nb:
-            self._ws[dtype] = cur = torch.empty(max(int(nb), 1), dtype=torch.uint8, device=self.device)
-        return cur, int(nb)
+            self._ws[dtype] = cur = torch.empty(max(nb, 1), dtype=torch.uint8, device=self.device)
+        return cur, nb
 
     def __del__(self):
         try:
@@ -282,10 +353,8 @@ class DecoderEngine(_Engine):
         if out is None:
             out = torch.empty(B, 1, Lw, dtype=torch.float32, device=dev)
         ws, nb = self.model.workspace(self.dtype, B, T)
-        rc = lib().stts_decoder_fwd(self.model.h, DTYPES[self.dtype], _ptr(asr), _ptr(F0_curve), _ptr(N), _ptr(s),
-                                    _ptr(noise), int(seed) & (2 ** 64 - 1), int(utt_offset), B, T, _ptr(out),
-                                    _ptr(ws), nb, _stream())
-        check(rc, "stts_decoder_fwd")
+        call("stts_decoder_fwd", self.model.h, DTYPES[self.dtype], asr, F0_curve, N, s, noise,
+             int(seed) & (2 ** 64 - 1), int(utt_offset), B, T, out, ws, nb)
         return out if in_dev.type == "cuda" else out.to(in_dev)
 
 
@@ -311,8 +380,7 @@ class F0NEngine(_Engine):
         F0 = torch.empty(B, 2 * T, dtype=torch.float32, device=dev)
         Nn = torch.empty(B, 2 * T, dtype=torch.float32, device=dev)
         ws, nb = self.model.workspace(self.dtype, B, T)
-        check(lib().stts_f0n_fwd(self.model.h, DTYPES[self.dtype], _ptr(x), _ptr(s), B, T, _ptr(F0), _ptr(Nn),
-                                 _ptr(ws), nb, _stream()), "stts_f0n_fwd")
+        call("stts_f0n_fwd", self.model.h, DTYPES[self.dtype], x, s, B, T, F0, Nn, ws, nb)
         if in_dev.type != "cuda":
             return F0.to(in_dev), Nn.to(in_dev)
         return F0, Nn
@@ -338,8 +406,7 @@ class StyleEngine(_Engine):
             raise ValueError(f"mel must be [B, 1, 80, T], got {tuple(mel.shape)}")
         out = torch.empty(B, self.style_dim, dtype=torch.float32, device=dev)
         ws, nb = self.model.workspace(self.dtype, B, T)
-        check(lib().stts_style_fwd(self.model.h, DTYPES[self.dtype], _ptr(mel), B, T, _ptr(out), _ptr(ws), nb,
-                                   _stream()), "stts_style_fwd")
+        call("stts_style_fwd", self.model.h, DTYPES[self.dtype], mel, B, T, out, ws, nb)
         return out if in_dev.type == "cuda" else out.to(in_dev)
 
 
@@ -367,12 +434,9 @@ class PitchEngine(_Engine):
         gan = torch.empty(B, 256, 10, T, dtype=torch.float32, device=dev) if features else None
         pool = torch.empty(B, 256, T, 2, dtype=torch.float32, device=dev) if features else None
         ws, nb = self.model.workspace(self.dtype, B, T)
-        L = lib()
-        check(L.stts_pitch_fwd(self.model.h, DTYPES[self.dtype], _ptr(mel), B, T, _ptr(f0), _ptr(gan), _ptr(pool),
-                               _ptr(ws), nb, _stream()), "stts_pitch_fwd")
+        call("stts_pitch_fwd", self.model.h, DTYPES[self.dtype], mel, B, T, f0, gan, pool, ws, nb)
         # the cooperative BiLSTM recurrence's time-out word, checked with the other BiLSTM launches' words
-        off = int(L.stts_pitch_error_offset(self.model.h, DTYPES[self.dtype], B, T))
-        check(off if off < 0 else 0, "stts_pitch_error_offset")
+        off = query("stts_pitch_error_offset", self.model.h, DTYPES[self.dtype], B, T)
         if len(prosody._PENDING) >= 64:
             prosody.check_pending()
         prosody._PENDING.append((f"JDCNet bilstm_classifier B={B} T={T}", ws[off:off + 4].view(torch.int32).clone()))
@@ -394,7 +458,7 @@ def log_norm(x, mean=-4, std=4, dim=2):
     B, _, M, T = m.shape
     out = torch.empty(B, 1, T, dtype=torch.float32, device=dev)
     if B and T:
-        check(lib().stts_log_norm(_ptr(m), B, M, T, float(mean), float(std), _ptr(out), _stream()), "stts_log_norm")
+        call("stts_log_norm", m, B, M, T, mean, std, out)
     return out if in_dev.type == "cuda" else out.to(in_dev)
 
 
@@ -421,12 +485,10 @@ class _DiscEngine(_Engine):
         out, B2, T = self.last
         if B2 % 2:
             raise ValueError("the last forward's batch is not real + generated halves")
-        nb = int(lib().stts_gan_losses_scratch_bytes(self.model.h))
-        check(nb if nb < 0 else 0, "stts_gan_losses_scratch_bytes")
+        nb = query("stts_gan_losses_scratch_bytes", self.model.h)
         scratch = torch.empty(nb // 8, dtype=torch.float64, device=out.device)
         loss = torch.empty(3, dtype=torch.float64, device=out.device)
-        check(getattr(lib(), self.LOSSES)(self.model.h, B2 // 2, T, _ptr(out), _ptr(scratch), nb, _ptr(loss),
-                                          _stream()), self.LOSSES)
+        call(self.LOSSES, self.model.h, B2 // 2, T, out, scratch, nb, loss)
         return loss
 
 
@@ -452,12 +514,10 @@ class MPDEngine(_DiscEngine):
         for p in self.periods:
             if (-T) % p >= T:
                 raise ValueError(f"T = {T} too short for the period-{p} reflect pad")
-        n = lib().stts_mpd_out_elems(self.model.h, B, T)
-        check(int(n) if n < 0 else 0, "stts_mpd_out_elems")
-        out = torch.empty(int(n), dtype=torch.float32, device=dev)
+        n = query("stts_mpd_out_elems", self.model.h, B, T)
+        out = torch.empty(n, dtype=torch.float32, device=dev)
         ws, nb = self.model.workspace(self.dtype, B, T)
-        check(lib().stts_mpd_fwd(self.model.h, DTYPES[self.dtype], _ptr(w), B, T, _ptr(out), int(n), _ptr(ws), nb,
-                                 _stream()), "stts_mpd_fwd")
+        call("stts_mpd_fwd", self.model.h, DTYPES[self.dtype], w, B, T, out, n, ws, nb)
         self.last = (out, B, T)
         res, off = [], 0
         for p in self.periods:
@@ -511,12 +571,10 @@ class MSDEngine(_DiscEngine):
             if T <= n_fft // 2:  # torch.stft's reflect pad
                 raise ValueError(f"T = {T} too short for n_fft {n_fft}")
         w = w.contiguous()
-        n = lib().stts_msd_out_elems(self.model.h, B, T)
-        check(int(n) if n < 0 else 0, "stts_msd_out_elems")
-        out = torch.empty(int(n), dtype=torch.float32, device=dev)
+        n = query("stts_msd_out_elems", self.model.h, B, T)
+        out = torch.empty(n, dtype=torch.float32, device=dev)
         ws, nb = self.model.workspace(self.dtype, B, T)
-        check(lib().stts_msd_fwd(self.model.h, DTYPES[self.dtype], _ptr(w), B, T, _ptr(out), int(n), _ptr(ws), nb,
-                                 _stream()), "stts_msd_fwd")
+        call("stts_msd_fwd", self.model.h, DTYPES[self.dtype], w, B, T, out, n, ws, nb)
         self.last = (out, B, T)
         res, off = [], 0
         for n_fft, hop, _ in self.res:
@@ -550,19 +608,17 @@ def wave_preprocess_batch(wave):
                          f"{MEL_NFFT // 2}")
     F = int(lib().stts_mel_frames(L))
     out = torch.empty(B, N_MELS, F, dtype=torch.float32, device=dev)
-    nb = int(lib().stts_mel_workspace_bytes())
-    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
-    check(lib().stts_wave_preprocess(_ptr(w), B, L, L, _ptr(out), _ptr(ws), nb, _stream()), "stts_wave_preprocess")
+    call("stts_wave_preprocess", w, B, L, L, out, ws=("stts_mel_workspace_bytes",))
     return out
 
 
 def profile_enable(on: bool = True):
-    check(lib().stts_profile_enable(1 if on else 0))
+    call("stts_profile_enable", 1 if on else 0)
 
 
 def profile_read():
     t, n, f, b = ctypes.c_double(), c_ll(), ctypes.c_double(), ctypes.c_double()
-    check(lib().stts_profile_read(ctypes.byref(t), ctypes.byref(n), ctypes.byref(f), ctypes.byref(b)))
+    call("stts_profile_read", ctypes.byref(t), ctypes.byref(n), ctypes.byref(f), ctypes.byref(b))
     return {"ms": t.value, "launches": n.value, "flops": f.value, "bytes": b.value}
 
 
@@ -577,7 +633,7 @@ def profile_launches():
     n = profile_read()["launches"]
     shape, v = (ctypes.c_int * 8)(), (ctypes.c_double * 3)()
     for i in range(n):
-        check(lib().stts_profile_launch(i, shape, v))
+        call("stts_profile_launch", i, shape, v)
         out.append({"B": shape[0], "rows": shape[1], "N": shape[2], "Cin": shape[3], "taps": shape[4],
                     "dil": shape[5], "Lout": shape[6], "res_acc": shape[7] & 3,
                     "kernel": ENGINE_KERNELS[(shape[7] >> 4) & 7], "ms": v[0], "flops": v[1], "bytes": v[2]})

@@ -19,9 +19,9 @@ import ctypes
 import torch
 from torch import nn
 
-from .engine import _ptr, _require_device, _stream, check, lib
+from .engine import _require_device, _workspace, call
 from .engine import log_norm  # noqa: F401  (utils.py:48-53, the N_real target of train.py:262)
-from .training import _f32, _workspace, _ws
+from .training import _c
 
 GAN_FEATURE, GAN_GEN, GAN_DISC, GAN_TPRLS = 0, 1, 2, 3
 
@@ -53,13 +53,11 @@ class _GanFn(torch.autograd.Function):
         for i, k in enumerate(kinds):
             a, b = ts[2 * i], ts[2 * i + 1]
             terms[i] = _GanTerm(a.data_ptr(), b.data_ptr(), a.numel(), int(k))
-        nb = lib().stts_gan_workspace_bytes(n)
-        check(int(nb) if nb < 0 else 0, "stts_gan_workspace_bytes")
-        ws = _ws(nb, ts[0].device)
+        ws, nb = _workspace("stts_gan_workspace_bytes", ts[0].device, n)  # (the backward reads it again)
         loss = torch.empty(1, dtype=torch.float64, device=ts[0].device)
-        check(lib().stts_gan_loss(terms, n, _ptr(loss), _ptr(ws), int(nb), _stream()), "stts_gan_loss")
+        call("stts_gan_loss", terms, n, loss, ws, nb)
         ctx.save_for_backward(*ts)
-        ctx.kinds, ctx.ws, ctx.nb = kinds, ws, int(nb)
+        ctx.kinds, ctx.ws, ctx.nb = kinds, ws, nb
         return loss[0].to(torch.float32)
 
     @staticmethod
@@ -80,9 +78,8 @@ class _GanFn(torch.autograd.Function):
             da[i] = ga.data_ptr() if ga is not None else None
             db[i] = gb.data_ptr() if gb is not None else None
             grads += [ga, gb]
-        g = _f32(go.reshape(1))
-        check(lib().stts_gan_loss_bwd(terms, da, db, n, _ptr(g), _ptr(ctx.ws), ctx.nb, _stream()),
-              "stts_gan_loss_bwd")
+        g = _c(go.reshape(1))
+        call("stts_gan_loss_bwd", terms, da, db, n, g, ctx.ws, ctx.nb)
         return (None, *grads)
 
 
@@ -175,12 +172,10 @@ class _MrstftFn(torch.autograd.Function):
         n = len(mod.fft_sizes)
         arr = lambda v: (ctypes.c_int * n)(*[int(t) for t in v])  # noqa: E731
         ffts, hops, wins = arr(mod.fft_sizes), arr(mod.hop_sizes), arr(mod.win_lengths)
-        xc, yc = _f32(x2), _f32(y2)
-        dev = xc.device
-        ws, nb = _workspace("stts_mrstft_workspace_bytes", dev, B, L, hops, n, mod.n_mels)
-        loss = torch.empty(1, dtype=torch.float64, device=dev)
-        check(lib().stts_mrstft_loss(_ptr(xc), _ptr(yc), B, L, L, ffts, hops, wins, n, mod.sample_rate, mod.n_mels,
-                                     _ptr(loss), _ptr(ws), int(nb), _stream()), "stts_mrstft_loss")
+        xc, yc = _c(x2), _c(y2)
+        loss = torch.empty(1, dtype=torch.float64, device=xc.device)
+        call("stts_mrstft_loss", xc, yc, B, L, L, ffts, hops, wins, n, mod.sample_rate, mod.n_mels, loss,
+             ws=("stts_mrstft_workspace_bytes", B, L, hops, n, mod.n_mels))
         ctx.save_for_backward(xc, yc)
         ctx.mod = mod
         return loss[0].to(torch.float32)
@@ -198,12 +193,10 @@ class _MrstftFn(torch.autograd.Function):
         n = len(mod.fft_sizes)
         arr = lambda v: (ctypes.c_int * n)(*[int(t) for t in v])  # noqa: E731
         ffts, hops, wins = arr(mod.fft_sizes), arr(mod.hop_sizes), arr(mod.win_lengths)
-        ws, nb = _workspace("stts_mrstft_bwd_workspace_bytes", xc.device, B, L, ffts, hops, wins, n, mod.n_mels)
         dx = torch.empty_like(xc)
-        g = _f32(go.reshape(1))
-        check(lib().stts_mrstft_loss_bwd(_ptr(xc), _ptr(yc), B, L, L, ffts, hops, wins, n, mod.sample_rate,
-                                         mod.n_mels, _ptr(g), _ptr(dx), _ptr(ws), int(nb), _stream()),
-              "stts_mrstft_loss_bwd")
+        g = _c(go.reshape(1))
+        call("stts_mrstft_loss_bwd", xc, yc, B, L, L, ffts, hops, wins, n, mod.sample_rate, mod.n_mels, g, dx,
+             ws=("stts_mrstft_bwd_workspace_bytes", B, L, ffts, hops, wins, n, mod.n_mels))
         return dx, None, None
 
 
@@ -236,11 +229,11 @@ class _SmoothL1Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, y):
         _require_device()
-        xc, yc = _f32(x), _f32(y)
+        xc, yc = _c(x), _c(y)
         if xc.shape != yc.shape:
             raise ValueError(f"smooth_l1_loss: {tuple(xc.shape)} vs {tuple(yc.shape)}")
         loss = torch.empty(1, dtype=torch.float64, device=xc.device)
-        check(lib().stts_smooth_l1_loss(_ptr(xc), _ptr(yc), xc.numel(), _ptr(loss), _stream()), "stts_smooth_l1_loss")
+        call("stts_smooth_l1_loss", xc, yc, xc.numel(), loss)
         ctx.save_for_backward(xc, yc)
         return loss[0].to(torch.float32)
 
@@ -248,11 +241,10 @@ class _SmoothL1Fn(torch.autograd.Function):
     def backward(ctx, g):
         xc, yc = ctx.saved_tensors
         nx, ny = ctx.needs_input_grad
-        gd = _f32(g.reshape(1))
+        gd = _c(g.reshape(1))
         dx = torch.empty_like(xc) if nx else None
         dy = torch.empty_like(yc) if ny else None
-        check(lib().stts_smooth_l1_loss_bwd(_ptr(xc), _ptr(yc), xc.numel(), _ptr(gd), _ptr(dx), _ptr(dy), _stream()),
-              "stts_smooth_l1_loss_bwd")
+        call("stts_smooth_l1_loss_bwd", xc, yc, xc.numel(), gd, dx, dy)
         return dx, dy
 
 

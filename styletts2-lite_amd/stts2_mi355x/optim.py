@@ -16,7 +16,7 @@ from functools import reduce
 import torch
 from torch.autograd.graph import increment_version
 
-from .engine import _require_device, _stream, check, lib
+from .engine import _require_device, call
 
 
 class _AdamWTensor(ctypes.Structure):
@@ -104,10 +104,7 @@ class AdamW(torch.optim.Optimizer):
         arr = (_AdamWTensor * len(items))()
         for i, (p, g, m, v) in enumerate(items):
             arr[i] = _AdamWTensor(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel())
-        check(lib().stts_adamw_step_dev(arr, len(items), ctypes.c_double(group["lr"]), ctypes.c_double(beta1),
-                                        ctypes.c_double(beta2), ctypes.c_double(group["eps"]),
-                                        ctypes.c_double(group["weight_decay"]), ctypes.c_void_p(dev.data_ptr()),
-                                        _stream()), "stts_adamw_step_dev")
+        call("stts_adamw_step_dev", arr, len(items), group["lr"], beta1, beta2, group["eps"], group["weight_decay"], dev)
         increment_version([p for p, _, _, _ in items])
 
     @torch.no_grad()
@@ -156,10 +153,8 @@ class AdamW(torch.optim.Optimizer):
                 arr = (_AdamWTensor * len(items))()
                 for i, (p, g, m, v) in enumerate(items):
                     arr[i] = _AdamWTensor(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel())
-                check(lib().stts_adamw_step(arr, len(items), ctypes.c_double(group["lr"]), ctypes.c_double(beta1),
-                                            ctypes.c_double(beta2), ctypes.c_double(group["eps"]),
-                                            ctypes.c_double(group["weight_decay"]), step, _stream()),
-                      "stts_adamw_step")
+                call("stts_adamw_step", arr, len(items), group["lr"], beta1, beta2, group["eps"],
+                     group["weight_decay"], step)
                 # the kernel writes through raw pointers: bump each parameter's version counter as torch's
                 # in-place update would, so cached packed weights (engine._Engine.stale) see the new values
                 increment_version([p for p, _, _, _ in items])

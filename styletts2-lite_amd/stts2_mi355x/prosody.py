@@ -21,19 +21,20 @@ import torch
 import torch.nn as nn
 from torch.nn.utils.rnn import PackedSequence, pack_padded_sequence, pad_packed_sequence
 
-from .engine import _ptr, _stream, check, lib
+from .engine import _ptr, _stream, check  # noqa: F401  (tests reach the raw library through this module)
+from .engine import _workspace, call, lib
 
 
 def set_lstm_group(bg: int) -> None:
     """BiLSTM recurrence kernel: 0 = automatic, -1 = cooperative (H = 256), 1 / 2 / 4 = utterances per
     workgroup of the per-workgroup kernel (A/B testing)."""
-    check(lib().stts_set_lstm_group(int(bg)), "stts_set_lstm_group")
+    call("stts_set_lstm_group", int(bg))
 
 
 def set_bilstm_debug(spin_limit: int = 0, drop: bool = False) -> None:
     """Testing hook of the cooperative recurrence (stts_set_bilstm_debug): waits give up after
     `spin_limit` polls (0 = the default bound) and, with `drop`, one workgroup never publishes."""
-    check(lib().stts_set_bilstm_debug(int(spin_limit), 1 if drop else 0), "stts_set_bilstm_debug")
+    call("stts_set_bilstm_debug", int(spin_limit), 1 if drop else 0)
 
 
 # device error words of BiLSTM launches not yet read by the host (stts_bilstm_error_offset)
@@ -78,8 +79,7 @@ def frames_gemm(x, xs, B, Tin, Cin, w, wst, N, K, pad, bias, bias2, y, ys, Tout)
     tiles = ((Tout + 63) // 64) * ((N + 63) // 64) * B
     elems = 16 * B * Tout * N if tiles < 128 and Cin * K >= 256 else 0
     ws = torch.empty(elems, dtype=torch.float32, device=y.device) if elems else None
-    check(lib().stts_frames_gemm_ws(_ptr(x), *xs, B, Tin, Cin, _ptr(w), *wst, N, K, pad, _ptr(bias), _ptr(bias2),
-                                    _ptr(y), *ys, Tout, _ptr(ws), elems * 4, _stream()), "stts_frames_gemm_ws")
+    call("stts_frames_gemm_ws", x, *xs, B, Tin, Cin, w, *wst, N, K, pad, bias, bias2, y, *ys, Tout, ws, elems * 4)
 
 
 def matmul(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
@@ -116,16 +116,15 @@ def row_norm(x, C, mode, gamma=None, beta=None, gb_sb=0, eps=1e-5, slope=None, l
     B, T = x.shape[0], x.shape[1]
     E = 0 if extra is None else extra.shape[1]
     y = torch.empty(B, T, C + E, dtype=torch.float32, device=x.device)
-    check(lib().stts_row_norm(_ptr(x), x.stride(0), x.stride(1), x.stride(2), B, T, C, mode, _ptr(gamma), _ptr(beta),
-                              gb_sb, eps, 0 if slope is None else 1, 0.0 if slope is None else slope, _ptr(lengths),
-                              _ptr(extra), E, _ptr(y), y.stride(0), y.stride(1), _stream()), "stts_row_norm")
+    call("stts_row_norm", x, x.stride(0), x.stride(1), x.stride(2), B, T, C, mode, gamma, beta, gb_sb, eps,
+         0 if slope is None else 1, 0.0 if slope is None else slope, lengths, extra, E, y, y.stride(0), y.stride(1))
     return y
 
 
 def weight_norm_fold(g: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
     w = torch.empty_like(v)
     d0 = v.shape[0]
-    check(lib().stts_weight_norm(_ptr(g), _ptr(v), d0, v.numel() // d0, _ptr(w), _stream()), "stts_weight_norm")
+    call("stts_weight_norm", g, v, d0, v.numel() // d0, w)
     return w
 
 
@@ -144,9 +143,8 @@ def durations(logits, lengths=None, z=None, mix=0.0, prev_mean=0.0, speed=1.0):
     pred = torch.empty(B, T, dtype=torch.int32, device=dev)
     total = torch.empty(B, dtype=torch.int32, device=dev)
     dmean = torch.empty(B, dtype=torch.float32, device=dev)
-    check(lib().stts_durations(_ptr(logits), logits.stride(0), logits.stride(1), B, T, K, _ptr(ln), _ptr(z),
-                               float(mix), float(prev_mean), float(speed), _ptr(dur), _ptr(pred), _ptr(total),
-                               _ptr(dmean), _stream()), "stts_durations")
+    call("stts_durations", logits, logits.stride(0), logits.stride(1), B, T, K, ln, z, mix, prev_mean, speed, dur, pred,
+         total, dmean)
     return dur, pred, total, dmean
 
 
@@ -158,8 +156,7 @@ def expand_frames(src_btc: torch.Tensor, pred: torch.Tensor, Fmax: int) -> torch
     pred = pred.to(torch.int32).contiguous()
     y = torch.empty(B, C, Fmax, dtype=torch.float32, device=src_btc.device)
     ftok = torch.empty(B, max(Fmax, 1), dtype=torch.int32, device=src_btc.device)
-    check(lib().stts_expand_frames(_ptr(src_btc), *src_btc.stride(), B, T, C, _ptr(pred), Fmax, _ptr(ftok), _ptr(y),
-                                   _stream()), "stts_expand_frames")
+    call("stts_expand_frames", src_btc, *src_btc.stride(), B, T, C, pred, Fmax, ftok, y)
     return y
 
 
@@ -210,15 +207,12 @@ class LSTM(nn.LSTM):
                   self.weight_hh_l0_reverse, self.bias_ih_l0_reverse, self.bias_hh_l0_reverse]
         params = [_on_device(p.detach(), "LSTM parameter").contiguous() for p in params]
         arr = (ctypes.c_void_p * 8)(*[p.data_ptr() for p in params])
-        L = lib()
-        nb = int(L.stts_bilstm_workspace_bytes(B, T, H))
-        ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=x.device)
+        ws, nb = _workspace("stts_bilstm_workspace_bytes", x.device, B, T, H)  # (its error word is read below)
         y = torch.empty(B, T, 2 * H, dtype=torch.float32, device=x.device)
         hn = torch.empty(2, B, H, dtype=torch.float32, device=x.device)
         cn = torch.empty(2, B, H, dtype=torch.float32, device=x.device)
-        check(L.stts_bilstm_fwd(_ptr(x), x.stride(0), x.stride(1), x.stride(2), B, T, Cin, _ptr(ln), arr, H, _ptr(y),
-                                _ptr(hn), _ptr(cn), _ptr(ws), nb, _stream()), "stts_bilstm_fwd")
-        off = int(L.stts_bilstm_error_offset(B, T, H))
+        call("stts_bilstm_fwd", x, x.stride(0), x.stride(1), x.stride(2), B, T, Cin, ln, arr, H, y, hn, cn, ws, nb)
+        off = int(lib().stts_bilstm_error_offset(B, T, H))
         if B > 0 and off >= 0:
             if len(_PENDING) >= 64:  # bound the list for callers that never sync through check_pending
                 check_pending()
@@ -303,8 +297,7 @@ class TextEncoder(nn.Module):
         h = torch.empty(B, T, C, dtype=torch.float32, device=dev)
         err = None if host_checked else torch.zeros(1, dtype=torch.int32, device=dev)
         emb = _on_device(self.embedding.weight.detach(), "embedding").contiguous()
-        check(lib().stts_embedding(_ptr(tok), B, T, _ptr(emb), self.n_symbols, C, _ptr(ln), _ptr(h), _ptr(err),
-                                   _stream()), "stts_embedding")
+        call("stts_embedding", tok, B, T, emb, self.n_symbols, C, ln, h, err)
         for blk in self.cnn:
             conv, ln_mod = blk[0], blk[1]
             w = self._folded(conv)

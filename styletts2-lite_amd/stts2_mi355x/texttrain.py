@@ -22,9 +22,9 @@ from __future__ import annotations
 
 import torch
 
-from .engine import _ptr, _require_device, _stream, check, lib
-from .prosody import _lengths, frames_gemm
-from .training import _c, _workspace, conv1d_frames, dropout, linear, weight_norm
+from .engine import _require_device, call
+from .prosody import _lengths
+from .training import _c, conv1d_frames, dropout, linear, weight_norm
 
 
 def needs_grad(module, *inputs) -> bool:
@@ -45,8 +45,7 @@ class _EmbeddingFn(torch.autograd.Function):
         wc = _c(weight)
         h = torch.empty(B, T, C, dtype=torch.float32, device=weight.device)
         err = torch.zeros(1, dtype=torch.int32, device=weight.device)
-        check(lib().stts_embedding(_ptr(tok), B, T, _ptr(wc), n_sym, C, _ptr(ln), _ptr(h), _ptr(err), _stream()),
-              "stts_embedding")
+        call("stts_embedding", tok, B, T, wc, n_sym, C, ln, h, err)
         ctx.save_for_backward(tok, ln if ln is not None else torch.empty(0))
         ctx.has_ln, ctx.shape = ln is not None, (n_sym, C)
         ctx.err = err
@@ -60,8 +59,7 @@ class _EmbeddingFn(torch.autograd.Function):
         B, T = tok.shape
         dhc = _c(dh)
         dW = torch.empty(n_sym, C, dtype=torch.float32, device=dh.device)
-        check(lib().stts_embedding_bwd(_ptr(tok), B, T, _ptr(ln), _ptr(dhc), dhc.stride(0), dhc.stride(1), n_sym, C,
-                                       _ptr(dW), _stream()), "stts_embedding_bwd")
+        call("stts_embedding_bwd", tok, B, T, ln, dhc, dhc.stride(0), dhc.stride(1), n_sym, C, dW)
         return dW, None, None
 
 
@@ -78,12 +76,11 @@ class _RowNormFn(torch.autograd.Function):
         xc = _c(x)
         g = _c(gamma if mode == 0 else gb) if mode != 2 else None
         bt = _c(beta) if mode == 0 else None
-        ex = _c(extra) if extra is not None else None
+        ex = _c(extra)
         y = torch.empty(B, T, C + E, dtype=torch.float32, device=x.device)
         gb_sb = g.stride(0) if mode == 1 else 0
-        check(lib().stts_row_norm(_ptr(xc), xc.stride(0), xc.stride(1), xc.stride(2), B, T, C, mode, _ptr(g), _ptr(bt),
-                                  gb_sb, eps, 0 if slope is None else 1, 0.0 if slope is None else slope, _ptr(ln),
-                                  _ptr(ex), E, _ptr(y), y.stride(0), y.stride(1), _stream()), "stts_row_norm")
+        call("stts_row_norm", xc, xc.stride(0), xc.stride(1), xc.stride(2), B, T, C, mode, g, bt, gb_sb, eps,
+             0 if slope is None else 1, 0.0 if slope is None else slope, ln, ex, E, y, y.stride(0), y.stride(1))
         ctx.save_for_backward(xc, *(t if t is not None else torch.empty(0) for t in (g, bt, ln)))
         ctx.cfg = (mode, eps, slope, E, ln is not None, gb_sb)
         return y
@@ -101,13 +98,10 @@ class _RowNormFn(torch.autograd.Function):
         dbeta = torch.empty(C, dtype=torch.float32, device=dy.device) if (mode == 0 and need[2]) else None
         dgb = torch.empty(B, 2 * C, dtype=torch.float32, device=dy.device) if (mode == 1 and need[3]) else None
         dex = torch.empty(B, E, dtype=torch.float32, device=dy.device) if (E and need[4]) else None
-        L = lib()
-        ws, nb = _workspace("stts_row_norm_bwd_workspace_bytes", dy.device, B, T, C)
-        check(L.stts_row_norm_bwd(_ptr(xc), xc.stride(0), xc.stride(1), xc.stride(2), B, T, C, mode,
-                                  _ptr(g if mode != 2 else None), _ptr(bt if mode == 0 else None), gb_sb, eps,
-                                  0 if slope is None else 1, 0.0 if slope is None else slope, _ptr(ln), _ptr(dyc),
-                                  dyc.stride(0), dyc.stride(1), E, _ptr(dx), _ptr(dgamma), _ptr(dbeta), _ptr(dgb),
-                                  _ptr(dex), _ptr(ws), nb, _stream()), "stts_row_norm_bwd")
+        call("stts_row_norm_bwd", xc, xc.stride(0), xc.stride(1), xc.stride(2), B, T, C, mode,
+             g if mode != 2 else None, bt if mode == 0 else None, gb_sb, eps, 0 if slope is None else 1,
+             0.0 if slope is None else slope, ln, dyc, dyc.stride(0), dyc.stride(1), E, dx, dgamma, dbeta, dgb, dex,
+             ws=("stts_row_norm_bwd_workspace_bytes", B, T, C))
         return dx, dgamma, dbeta, dgb, dex, None, None, None, None
 
 
@@ -169,10 +163,8 @@ class _DurLossFn(torch.autograd.Function):
         dc = _c(d)
         gt = _c(d_gt.to(torch.float32))
         loss = torch.empty(2, dtype=torch.float64, device=d.device)
-        L = lib()
-        ws, nb = _workspace("stts_dur_losses_workspace_bytes", d.device, B)
-        check(L.stts_dur_losses(_ptr(dc), dc.stride(0), dc.stride(1), B, T, K, _ptr(ln), _ptr(gt), gt.stride(0),
-                                _ptr(loss), None, None, None, _ptr(ws), nb, _stream()), "stts_dur_losses")
+        call("stts_dur_losses", dc, dc.stride(0), dc.stride(1), B, T, K, ln, gt, gt.stride(0), loss, None, None, None,
+             ws=("stts_dur_losses_workspace_bytes", B))
         ctx.save_for_backward(dc, gt, ln if ln is not None else torch.empty(0))
         ctx.has_ln = ln is not None
         out = loss.float()
@@ -188,10 +180,8 @@ class _DurLossFn(torch.autograd.Function):
         gc = _c(g_ce.reshape(1)) if g_ce is not None else None
         dz = torch.empty(B, T, K, dtype=torch.float32, device=dc.device)
         loss = torch.empty(2, dtype=torch.float64, device=dc.device)
-        L = lib()
-        ws, nb = _workspace("stts_dur_losses_workspace_bytes", dc.device, B)
-        check(L.stts_dur_losses(_ptr(dc), dc.stride(0), dc.stride(1), B, T, K, _ptr(ln), _ptr(gt), gt.stride(0),
-                                _ptr(loss), _ptr(dz), _ptr(gd), _ptr(gc), _ptr(ws), nb, _stream()), "stts_dur_losses")
+        call("stts_dur_losses", dc, dc.stride(0), dc.stride(1), B, T, K, ln, gt, gt.stride(0), loss, dz, gd, gc,
+             ws=("stts_dur_losses_workspace_bytes", B))
         return dz, None, None
 
 

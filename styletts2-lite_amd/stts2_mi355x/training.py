@@ -20,7 +20,7 @@ import math
 import torch
 from torch import nn
 
-from .engine import _ptr, _require_device, _stream, check, lib
+from .engine import _require_device, _workspace, call  # noqa: F401  (_workspace: texttrain, losses and tests import it)
 
 # bf16x3: the split-operand mode (fp32 frames, forward / dx operands as bf16 hi + lo, three MFMAs; dw in fp32)
 _DT = {"fp32": 0, "bf16": 1, "bf16x3": 2}
@@ -32,18 +32,6 @@ CONV_FLOPS = {"on": False, "fwd": 0.0, "bwd": 0.0}
 def _count(kind, flops):
     if CONV_FLOPS["on"]:
         CONV_FLOPS[kind] += flops
-
-
-def _ws(nbytes: int, device) -> torch.Tensor:
-    return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
-
-
-def _workspace(query: str, device, *args):
-    """(buffer, bytes) for a kernel whose size query is lib().<query>(*args); a negative size is the query's
-    STTS_E* code for these arguments and raises."""
-    nbytes = int(getattr(lib(), query)(*args))
-    check(nbytes if nbytes < 0 else 0, query)
-    return _ws(nbytes, device), nbytes
 
 
 def out_length(Lin: int, K: int, stride: int, pad: int, dil: int) -> int:
@@ -65,35 +53,28 @@ class _Conv1dFn(torch.autograd.Function):
         xf = x.detach().to(torch.float32).contiguous()
         wc = w.detach().to(torch.float32).contiguous()
         bc = bias.detach().to(torch.float32).contiguous() if bias is not None else None
-        ws, nb = _workspace("stts_conv1d_fwd_workspace_bytes", x.device, dt, B, Lin, Cin, Cout, K, stride, dil, pad, Lq)
+        geo = (B, Lin, Cin, Cout, K, stride, dil, pad, Lq)
+        ws = ("stts_conv1d_fwd_workspace_bytes", dt, *geo)
         y = torch.empty(B, Lq, Cout, dtype=torch.float32, device=x.device)
         ctx.scale = float(scale)
         ctx.act = act
         if act is not None:
             if res is not None or scale != 1.0:
                 raise ValueError("conv1d_frames: the fused leaky ReLU takes no residual / scale")
-            check(lib().stts_conv1d_fwd_act(dt, _ptr(xf), _ptr(wc), _ptr(bc), B, Lin, Cin, Cout, K, stride, dil, pad,
-                                            Lq, ctypes.c_float(act), _ptr(y), _ptr(ws), int(nb), _stream()),
-                  "stts_conv1d_fwd_act")
+            call("stts_conv1d_fwd_act", dt, xf, wc, bc, *geo, act, y, ws=ws)
         elif res is not None and dt != 0:
             # the residual epilogue of stts_conv1d_fwd_res is fp32-only: bf16 runs add it in a second pass
-            check(lib().stts_conv1d_fwd(dt, _ptr(xf), _ptr(wc), _ptr(bc), B, Lin, Cin, Cout, K, stride, dil, pad, Lq,
-                                        _ptr(y), _ptr(ws), int(nb), _stream()), "stts_conv1d_fwd")
+            call("stts_conv1d_fwd", dt, xf, wc, bc, *geo, y, ws=ws)
             rc = res.detach().to(torch.float32).contiguous()
             xs = (ctypes.c_void_p * 2)(y.data_ptr(), rc.data_ptr())
-            check(lib().stts_sum_div(xs, 2, y.numel(), ctypes.c_float(1.0 / scale), _ptr(y), _stream()),
-                  "stts_sum_div")
+            call("stts_sum_div", xs, 2, y.numel(), 1.0 / scale, y)
         elif res is not None or scale != 1.0:
             rc = res.detach().to(torch.float32).contiguous() if res is not None else None
-            check(lib().stts_conv1d_fwd_res(dt, _ptr(xf), _ptr(wc), _ptr(bc), _ptr(rc), ctypes.c_float(scale), B, Lin,
-                                            Cin, Cout, K, stride,
-                                            dil, pad, Lq, _ptr(y), _ptr(ws), int(nb), _stream()),
-                  "stts_conv1d_fwd_res")
+            call("stts_conv1d_fwd_res", dt, xf, wc, bc, rc, scale, *geo, y, ws=ws)
         else:
-            check(lib().stts_conv1d_fwd(dt, _ptr(xf), _ptr(wc), _ptr(bc), B, Lin, Cin, Cout, K, stride, dil, pad, Lq,
-                                        _ptr(y), _ptr(ws), int(nb), _stream()), "stts_conv1d_fwd")
+            call("stts_conv1d_fwd", dt, xf, wc, bc, *geo, y, ws=ws)
         ctx.save_for_backward(xf, wc, y if act is not None else None)
-        ctx.geo = (B, Lin, Cin, Cout, K, stride, dil, pad, Lq, dt, bias is not None)
+        ctx.geo = (*geo, dt, bias is not None)
         _count("fwd", 2.0 * B * Lq * Cout * Cin * K)
         return y
 
@@ -107,16 +88,14 @@ class _Conv1dFn(torch.autograd.Function):
         dyf = gy.detach().to(torch.float32).contiguous()
         if ctx.act is not None:  # through the fused leaky ReLU, on its output (the slope keeps the sign)
             dpre = torch.empty_like(dyf)
-            check(lib().stts_leaky_relu_bwd(_ptr(ya), _ptr(dyf), ya.numel(), ctypes.c_float(ctx.act), _ptr(dpre),
-                                            _stream()), "stts_leaky_relu_bwd")
+            call("stts_leaky_relu_bwd", ya, dyf, ya.numel(), ctx.act, dpre)
             dyf = dpre
         dev = dyf.device
-        ws, nb = _workspace("stts_conv1d_bwd_workspace_bytes", dev, dt, B, Lin, Cin, Cout, K, stride, dil, pad, Lq)
         dx = torch.empty(B, Lin, Cin, dtype=torch.float32, device=dev) if need_x else None
         dw = torch.empty(Cout, Cin, K, dtype=torch.float32, device=dev) if need_w else None
         db = torch.empty(Cout, dtype=torch.float32, device=dev) if (need_b and has_bias) else None
-        check(lib().stts_conv1d_bwd(dt, _ptr(xf), _ptr(wc), _ptr(dyf), B, Lin, Cin, Cout, K, stride, dil, pad, Lq,
-                                    _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws), int(nb), _stream()), "stts_conv1d_bwd")
+        call("stts_conv1d_bwd", dt, xf, wc, dyf, B, Lin, Cin, Cout, K, stride, dil, pad, Lq, dx, dw, db,
+             ws=("stts_conv1d_bwd_workspace_bytes", dt, B, Lin, Cin, Cout, K, stride, dil, pad, Lq))
         _count("bwd", 2.0 * B * Lq * Cout * Cin * K * ((dx is not None) + (dw is not None)))
         return dx, dw, db, None, None, None, None, (gy if ctx.needs_input_grad[7] else None), None, None
 
@@ -215,12 +194,9 @@ class _ConvT1dFn(torch.autograd.Function):
         Lout = (Lin - 1) * stride - 2 * pad + K + out_pad
         dt = _DT[dtype]
         xf, wc, bc = _c(x), _c(w), _c(bias)
-        ws, nb = _workspace("stts_conv_transpose1d_workspace_bytes", x.device, dt, B, Lin, Cin, Cout, K, stride, pad,
-                            Lout)
         y = torch.empty(B, Lout, Cout, dtype=torch.float32, device=x.device)
-        check(lib().stts_conv_transpose1d_fwd(dt, _ptr(xf), _ptr(wc), _ptr(bc), B, Lin, Cin, Cout, K, stride, pad,
-                                              Lout, _ptr(y), _ptr(ws), int(nb), _stream()),
-              "stts_conv_transpose1d_fwd")
+        call("stts_conv_transpose1d_fwd", dt, xf, wc, bc, B, Lin, Cin, Cout, K, stride, pad, Lout, y,
+             ws=("stts_conv_transpose1d_workspace_bytes", dt, B, Lin, Cin, Cout, K, stride, pad, Lout))
         ctx.save_for_backward(xf, wc)
         ctx.geo = (B, Lin, Cin, Cout, K, stride, pad, Lout, dt, bias is not None)
         _count("fwd", 2.0 * B * Lin * Cin * Cout * K)
@@ -232,14 +208,11 @@ class _ConvT1dFn(torch.autograd.Function):
         B, Lin, Cin, Cout, K, stride, pad, Lout, dt, has_bias = ctx.geo
         nx, nw, nbias = ctx.needs_input_grad[:3]
         dy = _c(gy)
-        ws, nb = _workspace("stts_conv_transpose1d_workspace_bytes", dy.device, dt, B, Lin, Cin, Cout, K, stride, pad,
-                            Lout)
         dx = torch.empty_like(xf) if nx else None
         dw = torch.empty_like(wc) if nw else None
         db = torch.empty(Cout, dtype=torch.float32, device=dy.device) if (nbias and has_bias) else None
-        check(lib().stts_conv_transpose1d_bwd(dt, _ptr(xf), _ptr(wc), _ptr(dy), B, Lin, Cin, Cout, K, stride, pad,
-                                              Lout, _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws), int(nb), _stream()),
-              "stts_conv_transpose1d_bwd")
+        call("stts_conv_transpose1d_bwd", dt, xf, wc, dy, B, Lin, Cin, Cout, K, stride, pad, Lout, dx, dw, db,
+             ws=("stts_conv_transpose1d_workspace_bytes", dt, B, Lin, Cin, Cout, K, stride, pad, Lout))
         _count("bwd", 2.0 * B * Lin * Cin * Cout * K * ((dx is not None) + (dw is not None)))
         return dx, dw, db, None, None, None, None
 
@@ -261,6 +234,7 @@ ACT_NONE, ACT_SNAKE, ACT_LRELU = 0, 1, 2
 
 
 def _c(t):
+    """t as a detached, contiguous float32 tensor (None stays None): what the kernels read."""
     return t.detach().to(torch.float32).contiguous() if t is not None else None
 
 
@@ -274,7 +248,7 @@ class _LinearFn(torch.autograd.Function):
         N = W.shape[0]
         sc, Wc, bc = _c(s), _c(W), _c(b)
         h = torch.empty(B, N, dtype=torch.float32, device=s.device)
-        check(lib().stts_linear_fwd(_ptr(sc), _ptr(Wc), _ptr(bc), B, K, N, _ptr(h), _stream()), "stts_linear_fwd")
+        call("stts_linear_fwd", sc, Wc, bc, B, K, N, h)
         ctx.save_for_backward(sc, Wc)
         ctx.has_b = b is not None
         return h
@@ -289,8 +263,7 @@ class _LinearFn(torch.autograd.Function):
         ds = torch.empty_like(sc) if ns else None
         dW = torch.empty_like(Wc) if nw else None
         db = torch.empty(N, dtype=torch.float32, device=dh.device) if (nb and ctx.has_b) else None
-        check(lib().stts_linear_bwd(_ptr(sc), _ptr(Wc), _ptr(dh), B, K, N, _ptr(ds), _ptr(dW), _ptr(db), _stream()),
-              "stts_linear_bwd")
+        call("stts_linear_bwd", sc, Wc, dh, B, K, N, ds, dW, db)
         return ds, dW, db
 
 
@@ -302,11 +275,9 @@ class _AdaINActFn(torch.autograd.Function):
         _require_device()
         B, L, C = x.shape
         xc, gbc, ac = _c(x), _c(gb), _c(alpha.reshape(-1)) if alpha is not None else None
-        ws, nb = _workspace("stts_adain_act_workspace_bytes", x.device, B, L, C)
         y = torch.empty_like(xc)
         mr = torch.empty(B, C, 2, dtype=torch.float32, device=x.device)
-        check(lib().stts_adain_act_fwd(_ptr(xc), _ptr(gbc), _ptr(ac), act, B, L, C, _ptr(y), _ptr(mr), _ptr(ws),
-                                       int(nb), _stream()), "stts_adain_act_fwd")
+        call("stts_adain_act_fwd", xc, gbc, ac, act, B, L, C, y, mr, ws=("stts_adain_act_workspace_bytes", B, L, C))
         ctx.save_for_backward(xc, gbc, ac if ac is not None else xc.new_empty(0), mr)
         ctx.act, ctx.alpha_shape = act, (alpha.shape if alpha is not None else None)
         return y
@@ -318,13 +289,11 @@ class _AdaINActFn(torch.autograd.Function):
         B, L, C = xc.shape
         dy = _c(dy)
         nx, ngb, na = ctx.needs_input_grad[:3]
-        ws, nb = _workspace("stts_adain_act_workspace_bytes", dy.device, B, L, C)
         dx = torch.empty_like(xc) if nx else None
         dgb = torch.empty_like(gbc) if ngb else None
         da = torch.empty(C, dtype=torch.float32, device=dy.device) if (na and act == ACT_SNAKE) else None
-        check(lib().stts_adain_act_bwd(_ptr(xc), _ptr(gbc), _ptr(ac if act == ACT_SNAKE else None), act, _ptr(mr),
-                                       _ptr(dy), B, L, C, _ptr(dx), _ptr(dgb), _ptr(da), _ptr(ws), int(nb),
-                                       _stream()), "stts_adain_act_bwd")
+        call("stts_adain_act_bwd", xc, gbc, ac if act == ACT_SNAKE else None, act, mr, dy, B, L, C, dx, dgb, da,
+             ws=("stts_adain_act_workspace_bytes", B, L, C))
         return dx, dgb, (da.reshape(ctx.alpha_shape) if da is not None else None), None
 
 
@@ -337,8 +306,7 @@ class _WeightNormFn(torch.autograd.Function):
         gc, vc = _c(g), _c(v)
         d0 = vc.shape[0]
         w = torch.empty_like(vc)
-        check(lib().stts_weight_norm(_ptr(gc), _ptr(vc), d0, vc.numel() // d0, _ptr(w), _stream()),
-              "stts_weight_norm")
+        call("stts_weight_norm", gc, vc, d0, vc.numel() // d0, w)
         ctx.save_for_backward(gc, vc)
         ctx.g_shape = g.shape
         return w
@@ -350,8 +318,7 @@ class _WeightNormFn(torch.autograd.Function):
         dw = _c(dw)
         dg = torch.empty(d0, dtype=torch.float32, device=dw.device)
         dv = torch.empty_like(vc)
-        check(lib().stts_weight_norm_bwd(_ptr(gc), _ptr(vc), _ptr(dw), d0, vc.numel() // d0, _ptr(dg), _ptr(dv),
-                                         _stream()), "stts_weight_norm_bwd")
+        call("stts_weight_norm_bwd", gc, vc, dw, d0, vc.numel() // d0, dg, dv)
         return dg.reshape(ctx.g_shape), dv
 
 
@@ -432,7 +399,7 @@ class _PoolFn(torch.autograd.Function):
         B, Lin, C = x.shape
         xc, wc, bc = _c(x), _c(w).reshape(C, 3), _c(bias)
         y = torch.empty(B, 2 * Lin, C, dtype=torch.float32, device=x.device)
-        check(lib().stts_pool_fwd(_ptr(xc), _ptr(wc), _ptr(bc), B, Lin, C, _ptr(y), _stream()), "stts_pool_fwd")
+        call("stts_pool_fwd", xc, wc, bc, B, Lin, C, y)
         ctx.save_for_backward(xc, wc)
         ctx.w_shape, ctx.has_b = w.shape, bias is not None
         return y
@@ -442,13 +409,11 @@ class _PoolFn(torch.autograd.Function):
         xc, wc = ctx.saved_tensors
         B, Lin, C = xc.shape
         dy = _c(gy)
-        nx, nw, nb_ = ctx.needs_input_grad
+        nx, nw, nb = ctx.needs_input_grad
         dx = torch.empty_like(xc) if nx else None
         dw = torch.empty(C, 3, dtype=torch.float32, device=dy.device) if nw else None
-        db = torch.empty(C, dtype=torch.float32, device=dy.device) if (nb_ and ctx.has_b) else None
-        ws, nb = _workspace("stts_pool_workspace_bytes", dy.device, B, Lin, C)
-        check(lib().stts_pool_bwd(_ptr(xc), _ptr(wc), _ptr(dy), B, Lin, C, _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws),
-                                  int(nb), _stream()), "stts_pool_bwd")
+        db = torch.empty(C, dtype=torch.float32, device=dy.device) if (nb and ctx.has_b) else None
+        call("stts_pool_bwd", xc, wc, dy, B, Lin, C, dx, dw, db, ws=("stts_pool_workspace_bytes", B, Lin, C))
         return dx, (dw.reshape(ctx.w_shape) if dw is not None else None), db
 
 
@@ -461,7 +426,7 @@ class _Up2Fn(torch.autograd.Function):
         B, Lin, C = x.shape
         xc = _c(x)
         y = torch.empty(B, 2 * Lin, C, dtype=torch.float32, device=x.device)
-        check(lib().stts_upsample2(_ptr(xc), B, Lin, C, _ptr(y), _stream()), "stts_upsample2")
+        call("stts_upsample2", xc, B, Lin, C, y)
         ctx.shape = (B, Lin, C)
         return y
 
@@ -470,7 +435,7 @@ class _Up2Fn(torch.autograd.Function):
         B, Lin, C = ctx.shape
         dy = _c(gy)
         dx = torch.empty(B, Lin, C, dtype=torch.float32, device=dy.device)
-        check(lib().stts_upsample2_bwd(_ptr(dy), B, Lin, C, _ptr(dx), _stream()), "stts_upsample2_bwd")
+        call("stts_upsample2_bwd", dy, B, Lin, C, dx)
         return dx
 
 
@@ -567,8 +532,7 @@ class _LReLUFn(torch.autograd.Function):
         _require_device()
         xc = _c(x)
         y = torch.empty_like(xc)
-        check(lib().stts_leaky_relu(_ptr(xc), xc.numel(), ctypes.c_float(slope), _ptr(y), _stream()),
-              "stts_leaky_relu")
+        call("stts_leaky_relu", xc, xc.numel(), slope, y)
         ctx.save_for_backward(y)
         ctx.slope = slope
         return y
@@ -578,8 +542,7 @@ class _LReLUFn(torch.autograd.Function):
         (y,) = ctx.saved_tensors
         dy = _c(gy)
         dx = torch.empty_like(y)
-        check(lib().stts_leaky_relu_bwd(_ptr(y), _ptr(dy), y.numel(), ctypes.c_float(ctx.slope), _ptr(dx),
-                                        _stream()), "stts_leaky_relu_bwd")
+        call("stts_leaky_relu_bwd", y, dy, y.numel(), ctx.slope, dx)
         return dx, None
 
 
@@ -645,10 +608,6 @@ class DiscriminatorP(nn.Module):
 # discriminators (Modules/discriminators.py) with theirs, the losses (losses.py) and AdamW (optimizers.py).
 # Every Function below runs its forward and backward as HIP kernels (include/stts2_train.h).
 
-def _f32(t):
-    return t.detach().to(torch.float32).contiguous()
-
-
 class _SnakeFn(torch.autograd.Function):
     """Snake with a learned alpha (the Generator's stage activations, hifigan.py:329, :343) on frames."""
 
@@ -656,9 +615,9 @@ class _SnakeFn(torch.autograd.Function):
     def forward(ctx, x, alpha):
         _require_device()
         B, L, C = x.shape
-        xc, ac = _f32(x), _f32(alpha.reshape(-1))
+        xc, ac = _c(x), _c(alpha.reshape(-1))
         y = torch.empty_like(xc)
-        check(lib().stts_snake_fwd(_ptr(xc), _ptr(ac), B, L, C, _ptr(y), _stream()), "stts_snake_fwd")
+        call("stts_snake_fwd", xc, ac, B, L, C, y)
         ctx.save_for_backward(xc, ac)
         ctx.a_shape = alpha.shape
         return y
@@ -668,12 +627,10 @@ class _SnakeFn(torch.autograd.Function):
         xc, ac = ctx.saved_tensors
         B, L, C = xc.shape
         nx, na = ctx.needs_input_grad
-        dyc = _f32(dy)
+        dyc = _c(dy)
         dx = torch.empty_like(xc) if nx else None
         da = torch.empty(C, dtype=torch.float32, device=dyc.device) if na else None
-        ws, nb = _workspace("stts_snake_workspace_bytes", dyc.device, B, L, C)
-        check(lib().stts_snake_bwd(_ptr(xc), _ptr(ac), _ptr(dyc), B, L, C, _ptr(dx), _ptr(da), _ptr(ws), int(nb),
-                                   _stream()), "stts_snake_bwd")
+        call("stts_snake_bwd", xc, ac, dyc, B, L, C, dx, da, ws=("stts_snake_workspace_bytes", B, L, C))
         return dx, (da.reshape(ctx.a_shape) if da is not None else None)
 
 
@@ -685,18 +642,18 @@ class _TanhFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
         _require_device()
-        xc = _f32(x)
+        xc = _c(x)
         y = torch.empty_like(xc)
-        check(lib().stts_tanh_fwd(_ptr(xc), xc.numel(), _ptr(y), _stream()), "stts_tanh_fwd")
+        call("stts_tanh_fwd", xc, xc.numel(), y)
         ctx.save_for_backward(y)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         (y,) = ctx.saved_tensors
-        dyc = _f32(dy)
+        dyc = _c(dy)
         dx = torch.empty_like(y)
-        check(lib().stts_tanh_bwd(_ptr(y), _ptr(dyc), y.numel(), _ptr(dx), _stream()), "stts_tanh_bwd")
+        call("stts_tanh_bwd", y, dyc, y.numel(), dx)
         return dx
 
 
@@ -710,13 +667,13 @@ class _SumDivFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, div, *xs):
         _require_device()
-        xc = [_f32(x) for x in xs]
+        xc = [_c(x) for x in xs]
         for x in xc[1:]:
             if x.shape != xc[0].shape:
                 raise ValueError(f"sum of tensors of shapes {[tuple(t.shape) for t in xc]}")
         y = torch.empty_like(xc[0])
         arr = (ctypes.c_void_p * len(xc))(*[x.data_ptr() for x in xc])
-        check(lib().stts_sum_div(arr, len(xc), y.numel(), ctypes.c_float(div), _ptr(y), _stream()), "stts_sum_div")
+        call("stts_sum_div", arr, len(xc), y.numel(), div, y)
         ctx.div, ctx.n = float(div), len(xc)
         return y
 
@@ -725,9 +682,9 @@ class _SumDivFn(torch.autograd.Function):
         if ctx.div == 1.0:
             g = dy
         else:
-            dyc = _f32(dy)
+            dyc = _c(dy)
             g = torch.empty_like(dyc)
-            check(lib().stts_div(_ptr(dyc), dyc.numel(), ctypes.c_float(ctx.div), _ptr(g), _stream()), "stts_div")
+            call("stts_div", dyc, dyc.numel(), ctx.div, g)
         # every input gets its own tensor: the inputs may come from concurrent branches (CONCURRENT_BRANCHES), and
         # autograd may accumulate a gradient in place on one stream while another branch's stream still reads a
         # shared one
@@ -750,23 +707,20 @@ class _SourceFn(torch.autograd.Function):
         _require_device()
         B, n = f0_curve.shape
         L = n * scale
-        fc, wc, bc = _f32(f0_curve), _f32(lw.reshape(-1)), _f32(lb.reshape(-1))
-        nz = _f32(noise) if noise is not None else None
+        fc, wc, bc = _c(f0_curve), _c(lw.reshape(-1)), _c(lb.reshape(-1))
+        nz = _c(noise)
         if nz is not None and tuple(nz.shape) != (B, L, 9):
             raise ValueError(f"noise {tuple(nz.shape)}: expected {(B, L, 9)}")
         sw = torch.empty(B, L, 9, dtype=torch.float32, device=fc.device)
         har = torch.empty(B, L, dtype=torch.float32, device=fc.device)
-        ws, nb = _workspace("stts_source_workspace_bytes", fc.device, B, n)
+        ws = ("stts_source_workspace_bytes", B, n)
         if isinstance(seed, torch.Tensor):  # a device int64 [1] (the capturable step): the kernel reads it
             if not seed.is_cuda or seed.dtype != torch.int64:
                 raise TypeError("seed tensor: int64 on the device")
-            check(lib().stts_source_fwd_seed_dev(_ptr(fc), _ptr(wc), _ptr(bc), _ptr(nz), _ptr(seed), int(utt_offset), B,
-                                                 n, int(scale), _ptr(sw), _ptr(har), _ptr(ws), int(nb), _stream()),
-                  "stts_source_fwd_seed_dev")
+            call("stts_source_fwd_seed_dev", fc, wc, bc, nz, seed, int(utt_offset), B, n, int(scale), sw, har, ws=ws)
         else:
-            check(lib().stts_source_fwd(_ptr(fc), _ptr(wc), _ptr(bc), _ptr(nz),
-                                        ctypes.c_ulonglong(int(seed) & (2**64 - 1)), int(utt_offset), B, n, int(scale),
-                                        _ptr(sw), _ptr(har), _ptr(ws), int(nb), _stream()), "stts_source_fwd")
+            call("stts_source_fwd", fc, wc, bc, nz, ctypes.c_ulonglong(int(seed) & (2**64 - 1)), int(utt_offset), B, n,
+                 int(scale), sw, har, ws=ws)
         ctx.save_for_backward(sw, har)
         ctx.shapes = (lw.shape, lb.shape, n)
         return har
@@ -779,12 +733,10 @@ class _SourceFn(torch.autograd.Function):
         nw, nbias = ctx.needs_input_grad[1:3]
         if not (nw or nbias):
             return (None,) * 7
-        d = _f32(dhar)
+        d = _c(dhar)
         dW = torch.empty(9, dtype=torch.float32, device=d.device)
         db = torch.empty(1, dtype=torch.float32, device=d.device)
-        ws, nbytes = _workspace("stts_source_workspace_bytes", d.device, B, n)
-        check(lib().stts_source_bwd(_ptr(sw), _ptr(har), _ptr(d), B, L, _ptr(dW), _ptr(db), _ptr(ws), int(nbytes),
-                                    _stream()), "stts_source_bwd")
+        call("stts_source_bwd", sw, har, d, B, L, dW, db, ws=("stts_source_workspace_bytes", B, n))
         return None, (dW.reshape(lw_shape) if nw else None), (db.reshape(lb_shape) if nbias else None), None, None, \
             None, None
 
@@ -795,19 +747,19 @@ class _BoxFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, k):
         _require_device()
-        xc = _f32(x)
+        xc = _c(x)
         B, n = xc.shape
         y = torch.empty_like(xc)
-        check(lib().stts_box_smooth_fwd(_ptr(xc), B, n, int(k), _ptr(y), _stream()), "stts_box_smooth_fwd")
+        call("stts_box_smooth_fwd", xc, B, n, int(k), y)
         ctx.k = int(k)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        d = _f32(dy)
+        d = _c(dy)
         B, n = d.shape
         dx = torch.empty_like(d)
-        check(lib().stts_box_smooth_bwd(_ptr(d), B, n, ctx.k, _ptr(dx), _stream()), "stts_box_smooth_bwd")
+        call("stts_box_smooth_bwd", d, B, n, ctx.k, dx)
         return dx, None
 
 
@@ -836,19 +788,19 @@ class _TimeExpandFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y):
         _require_device()
-        yc = _f32(y)
+        yc = _c(y)
         S, H, W, C = yc.shape
         x3 = torch.empty(S, H, W, 3 * C, dtype=torch.float32, device=yc.device)
-        check(lib().stts_time_expand3(_ptr(yc), S, H, W, C, _ptr(x3), _stream()), "stts_time_expand3")
+        call("stts_time_expand3", yc, S, H, W, C, x3)
         ctx.shape = (S, H, W, C)
         return x3
 
     @staticmethod
     def backward(ctx, dx3):
         S, H, W, C = ctx.shape
-        d = _f32(dx3)
+        d = _c(dx3)
         dy = torch.empty(S, H, W, C, dtype=torch.float32, device=d.device)
-        check(lib().stts_time_expand3_bwd(_ptr(d), S, H, W, C, _ptr(dy), _stream()), "stts_time_expand3_bwd")
+        call("stts_time_expand3_bwd", d, S, H, W, C, dy)
         return dy
 
 
@@ -869,21 +821,20 @@ class _ConvTxFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, w, bias, stride, pad, dtype, act):
         _require_device()
-        hf = _f32(h)
+        hf = _c(h)
         S, H, W, C = hf.shape
         co, ci, kh, kw = w.shape
         if ci != C or kh != 3:
             raise ValueError(f"weight {tuple(w.shape)} does not take the [S, H, W, {C}] image")
         Lq = out_length(W, kw, stride, pad, 1)
         dt = _DT[dtype]
-        wc = _f32(w)
+        wc = _c(w)
         wtx = wc.permute(0, 2, 1, 3).contiguous()  # [Cout][3][C][kw]: K index dh C + c
-        bc = _f32(bias) if bias is not None else None
-        ws, nb = _workspace("stts_conv1d_fwd_tx_workspace_bytes", hf.device, dt, S, H, W, C, co, kw, stride, pad, Lq)
+        bc = _c(bias)
         y = torch.empty(S * H, Lq, co, dtype=torch.float32, device=hf.device)
-        check(lib().stts_conv1d_fwd_tx(dt, _ptr(hf), _ptr(wtx), _ptr(bc), S, H, W, C, co, kw, stride, pad, Lq,
-                                       int(act is not None), ctypes.c_float(act if act is not None else 0.0), _ptr(y),
-                                       _ptr(ws), int(nb), _stream()), "stts_conv1d_fwd_tx")
+        call("stts_conv1d_fwd_tx", dt, hf, wtx, bc, S, H, W, C, co, kw, stride, pad, Lq, int(act is not None),
+             act if act is not None else 0.0, y,
+             ws=("stts_conv1d_fwd_tx_workspace_bytes", dt, S, H, W, C, co, kw, stride, pad, Lq))
         ctx.save_for_backward(hf, wc, y if act is not None else None)
         ctx.geo = (S, H, W, C, co, kw, stride, pad, Lq, dt, bias is not None)
         ctx.act = act
@@ -895,48 +846,43 @@ class _ConvTxFn(torch.autograd.Function):
         hf, wc, ya = ctx.saved_tensors
         S, H, W, C, co, kw, stride, pad, Lq, dt, has_bias = ctx.geo
         need_x, need_w, need_b = ctx.needs_input_grad[:3]
-        dyf = _f32(gy)
+        dyf = _c(gy)
         if ctx.act is not None:
             dpre = torch.empty_like(dyf)
-            check(lib().stts_leaky_relu_bwd(_ptr(ya), _ptr(dyf), ya.numel(), ctypes.c_float(ctx.act), _ptr(dpre),
-                                            _stream()), "stts_leaky_relu_bwd")
+            call("stts_leaky_relu_bwd", ya, dyf, ya.numel(), ctx.act, dpre)
             dyf = dpre
         dev = dyf.device
         B, Cin = S * H, 3 * C
         dh = None
         if need_x and co == 32:  # d h straight from dy (no dx3 image, no fold)
             wd = wc.flip(2).permute(2, 0, 1, 3).contiguous()  # [3][Cout][C][kw]: chunk j = row dh = 2 - j
-            ws, nb = _workspace("stts_conv1d_bwd_tx_workspace_bytes", dev, dt, S, H, W, C, co, kw, stride, pad, Lq)
             dh = torch.empty(S, H, W, C, dtype=torch.float32, device=dev)
-            check(lib().stts_conv1d_bwd_tx(dt, _ptr(dyf), _ptr(wd), S, H, W, C, co, kw, stride, pad, Lq, _ptr(dh),
-                                           _ptr(ws), int(nb), _stream()), "stts_conv1d_bwd_tx")
+            call("stts_conv1d_bwd_tx", dt, dyf, wd, S, H, W, C, co, kw, stride, pad, Lq, dh,
+                 ws=("stts_conv1d_bwd_tx_workspace_bytes", dt, S, H, W, C, co, kw, stride, pad, Lq))
             _count("bwd", 2.0 * B * Lq * co * Cin * kw)
             need_x = False
         need_b = need_b and has_bias
         dx3 = dw = db = None
         if not need_x and (need_w or need_b) and dt == 1 and (kw, stride) in _WGRAD_TX:  # bf16: no x3 either
-            ws, nb = _workspace("stts_conv1d_bwd_workspace_bytes", dev, dt, B, W, Cin, co, kw, stride, 1, pad, Lq)
             dwt = torch.empty(co, 3, C, kw, dtype=torch.float32, device=dev)
             db = torch.empty(co, dtype=torch.float32, device=dev) if need_b else None
-            check(lib().stts_conv1d_wgrad_tx(dt, _ptr(hf), _ptr(dyf), S, H, W, C, co, kw, stride, pad, Lq, _ptr(dwt),
-                                             _ptr(db), _ptr(ws), int(nb), _stream()), "stts_conv1d_wgrad_tx")
+            call("stts_conv1d_wgrad_tx", dt, hf, dyf, S, H, W, C, co, kw, stride, pad, Lq, dwt, db,
+                 ws=("stts_conv1d_bwd_workspace_bytes", dt, B, W, Cin, co, kw, stride, 1, pad, Lq))
             _count("bwd", 2.0 * B * Lq * co * Cin * kw)
             dw = dwt.permute(0, 2, 1, 3) if need_w else None  # -> [Cout][C][3][kw]
             need_w = need_b = False
         if need_x or need_w or need_b:  # (the G step's frozen discriminators skip this: d h only)
             x3 = torch.empty(S, H, W, Cin, dtype=torch.float32, device=dev)
-            check(lib().stts_time_expand3(_ptr(hf), S, H, W, C, _ptr(x3), _stream()), "stts_time_expand3")
-            ws, nb = _workspace("stts_conv1d_bwd_workspace_bytes", dev, dt, B, W, Cin, co, kw, stride, 1, pad, Lq)
+            call("stts_time_expand3", hf, S, H, W, C, x3)
             dx3 = torch.empty(B, W, Cin, dtype=torch.float32, device=dev) if need_x else None
             dw = torch.empty(co, Cin, kw, dtype=torch.float32, device=dev) if need_w else None
             db = torch.empty(co, dtype=torch.float32, device=dev) if need_b else None
-            check(lib().stts_conv1d_bwd(dt, _ptr(x3), _ptr(wc), _ptr(dyf), B, W, Cin, co, kw, stride, 1, pad, Lq,
-                                        _ptr(dx3), _ptr(dw), _ptr(db), _ptr(ws), int(nb), _stream()),
-                  "stts_conv1d_bwd")
+            call("stts_conv1d_bwd", dt, x3, wc, dyf, B, W, Cin, co, kw, stride, 1, pad, Lq, dx3, dw, db,
+                 ws=("stts_conv1d_bwd_workspace_bytes", dt, B, W, Cin, co, kw, stride, 1, pad, Lq))
             _count("bwd", 2.0 * B * Lq * co * Cin * kw * ((dx3 is not None) + (dw is not None)))
         if dx3 is not None:
             dh = torch.empty(S, H, W, C, dtype=torch.float32, device=dev)
-            check(lib().stts_time_expand3_bwd(_ptr(dx3), S, H, W, C, _ptr(dh), _stream()), "stts_time_expand3_bwd")
+            call("stts_time_expand3_bwd", dx3, S, H, W, C, dh)
         if dw is not None and dw.dim() == 3:
             dw = dw.reshape(co, C, 3, kw)
         return dh, dw, db, None, None, None, None
@@ -948,14 +894,13 @@ class _StftMagFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, wave, n_fft, hop, win):
         _require_device()
-        w = _f32(wave)
+        w = _c(wave)
         S, L = w.shape
         F_ = 1 + L // hop
         nb = n_fft // 2 + 1
         mag = torch.empty(S, F_, nb, dtype=torch.float32, device=w.device)
         spec = torch.empty(S, F_, nb, 2, dtype=torch.float32, device=w.device)
-        check(lib().stts_stft_mag_fwd(_ptr(w), S, L, L, n_fft, win, hop, _ptr(mag), _ptr(spec), _stream()),
-              "stts_stft_mag_fwd")
+        call("stts_stft_mag_fwd", w, S, L, L, n_fft, win, hop, mag, spec)
         ctx.save_for_backward(spec)
         ctx.geo = (S, L, n_fft, win, hop)
         return mag
@@ -964,11 +909,10 @@ class _StftMagFn(torch.autograd.Function):
     def backward(ctx, dmag):
         (spec,) = ctx.saved_tensors
         S, L, n_fft, win, hop = ctx.geo
-        d = _f32(dmag)
+        d = _c(dmag)
         dw = torch.empty(S, L, dtype=torch.float32, device=d.device)
-        ws, nb = _workspace("stts_stft_mag_workspace_bytes", d.device, S, L, n_fft, win, hop)
-        check(lib().stts_stft_mag_bwd(_ptr(spec), _ptr(d), S, L, n_fft, win, hop, _ptr(dw), _ptr(ws), int(nb),
-                                      _stream()), "stts_stft_mag_bwd")
+        call("stts_stft_mag_bwd", spec, d, S, L, n_fft, win, hop, dw,
+             ws=("stts_stft_mag_workspace_bytes", S, L, n_fft, win, hop))
         return dw, None, None, None
 
 
@@ -1109,10 +1053,9 @@ class _DWConvFn(torch.autograd.Function):
         _require_device()
         B, L, C = x.shape
         K = w.shape[-1]
-        xc, wc, bc = _f32(x), _f32(w).reshape(C, K), (_f32(bias) if bias is not None else None)
+        xc, wc, bc = _c(x), _c(w).reshape(C, K), _c(bias)
         y = torch.empty_like(xc)
-        check(lib().stts_dwconv1d_fwd(_ptr(xc), _ptr(wc), _ptr(bc), B, L, C, K, _ptr(y), _stream()),
-              "stts_dwconv1d_fwd")
+        call("stts_dwconv1d_fwd", xc, wc, bc, B, L, C, K, y)
         ctx.save_for_backward(xc, wc)
         ctx.w_shape, ctx.has_b = w.shape, bias is not None
         return y
@@ -1122,14 +1065,13 @@ class _DWConvFn(torch.autograd.Function):
         xc, wc = ctx.saved_tensors
         B, L, C = xc.shape
         K = wc.shape[1]
-        dy = _f32(gy)
+        dy = _c(gy)
         nx, nw, nbias = ctx.needs_input_grad
         dx = torch.empty_like(xc) if nx else None
         dw = torch.empty(C, K, dtype=torch.float32, device=dy.device) if nw else None
         db = torch.empty(C, dtype=torch.float32, device=dy.device) if (nbias and ctx.has_b) else None
-        ws, nb = _workspace("stts_dwconv1d_bwd_workspace_bytes", dy.device, B, L, C, K)
-        check(lib().stts_dwconv1d_bwd(_ptr(xc), _ptr(wc), _ptr(dy), B, L, C, K, _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws),
-                                      int(nb), _stream()), "stts_dwconv1d_bwd")
+        call("stts_dwconv1d_bwd", xc, wc, dy, B, L, C, K, dx, dw, db,
+             ws=("stts_dwconv1d_bwd_workspace_bytes", B, L, C, K))
         return dx, (dw.reshape(ctx.w_shape) if dw is not None else None), db
 
 
@@ -1143,18 +1085,18 @@ class _GeluFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
         _require_device()
-        xc = _f32(x)
+        xc = _c(x)
         y = torch.empty_like(xc)
-        check(lib().stts_gelu_fwd(_ptr(xc), xc.numel(), _ptr(y), _stream()), "stts_gelu_fwd")
+        call("stts_gelu_fwd", xc, xc.numel(), y)
         ctx.save_for_backward(xc)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         (xc,) = ctx.saved_tensors
-        dy = _f32(gy)
+        dy = _c(gy)
         dx = torch.empty_like(xc)
-        check(lib().stts_gelu_bwd(_ptr(xc), _ptr(dy), xc.numel(), _ptr(dx), _stream()), "stts_gelu_bwd")
+        call("stts_gelu_bwd", xc, dy, xc.numel(), dx)
         return dx
 
 
@@ -1169,12 +1111,11 @@ class _LayerScaleResFn(torch.autograd.Function):
     def forward(ctx, x, r, gamma):
         _require_device()
         B, L, C = x.shape
-        xc, rc, gc = _f32(x), _f32(r), _f32(gamma)
+        xc, rc, gc = _c(x), _c(r), _c(gamma)
         if rc.shape != xc.shape or gc.numel() != C:
             raise ValueError(f"layer scale: x {tuple(x.shape)}, r {tuple(r.shape)}, gamma {tuple(gamma.shape)}")
         y = torch.empty_like(xc)
-        check(lib().stts_layer_scale_res_fwd(_ptr(xc), _ptr(rc), _ptr(gc), B, L, C, _ptr(y), _stream()),
-              "stts_layer_scale_res_fwd")
+        call("stts_layer_scale_res_fwd", xc, rc, gc, B, L, C, y)
         ctx.save_for_backward(xc, gc)
         ctx.g_shape = gamma.shape
         return y
@@ -1183,13 +1124,12 @@ class _LayerScaleResFn(torch.autograd.Function):
     def backward(ctx, gy):
         xc, gc = ctx.saved_tensors
         B, L, C = xc.shape
-        dy = _f32(gy)
+        dy = _c(gy)
         nx, nr, ng = ctx.needs_input_grad
         dx = torch.empty_like(xc) if nx else None
         dg = torch.empty(C, dtype=torch.float32, device=dy.device) if ng else None
-        ws, nb = _workspace("stts_layer_scale_res_bwd_workspace_bytes", dy.device, B, L, C)
-        check(lib().stts_layer_scale_res_bwd(_ptr(xc), _ptr(gc), _ptr(dy), B, L, C, _ptr(dx), _ptr(dg), _ptr(ws),
-                                             int(nb), _stream()), "stts_layer_scale_res_bwd")
+        call("stts_layer_scale_res_bwd", xc, gc, dy, B, L, C, dx, dg,
+             ws=("stts_layer_scale_res_bwd_workspace_bytes", B, L, C))
         return dx, (gy if nr else None), (dg.reshape(ctx.g_shape) if dg is not None else None)
 
 
@@ -1207,11 +1147,9 @@ class _ISTFTHeadFn(torch.autograd.Function):
         B, F, W = h.shape
         if W != n_fft + 2 or window.numel() != n_fft:
             raise ValueError(f"ISTFT head: h {tuple(h.shape)}, window {tuple(window.shape)} for n_fft {n_fft}")
-        hc, wc = _f32(h), _f32(window)
-        ws, nb = _workspace("stts_istft_head_workspace_bytes", h.device, B, F, n_fft, hop)
+        hc, wc = _c(h), _c(window)
         y = torch.empty(B, F * hop, dtype=torch.float32, device=h.device)
-        check(lib().stts_istft_head_fwd(_ptr(hc), _ptr(wc), B, F, n_fft, hop, _ptr(y), _ptr(ws), int(nb), _stream()),
-              "stts_istft_head_fwd")
+        call("stts_istft_head_fwd", hc, wc, B, F, n_fft, hop, y, ws=("stts_istft_head_workspace_bytes", B, F, n_fft, hop))
         ctx.save_for_backward(hc, wc)
         ctx.geo = (n_fft, hop)
         return y
@@ -1221,10 +1159,9 @@ class _ISTFTHeadFn(torch.autograd.Function):
         hc, wc = ctx.saved_tensors
         n_fft, hop = ctx.geo
         B, F, _ = hc.shape
-        dy = _f32(gy)
+        dy = _c(gy)
         dh = torch.empty_like(hc)
-        check(lib().stts_istft_head_bwd(_ptr(hc), _ptr(wc), _ptr(dy), B, F, n_fft, hop, _ptr(dh), None, 0, _stream()),
-              "stts_istft_head_bwd")
+        call("stts_istft_head_bwd", hc, wc, dy, B, F, n_fft, hop, dh, None, 0)
         return dh, None, None, None
 
 
@@ -1286,14 +1223,13 @@ class _CSTFTFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, wave, wr, wi, n_fft, hop):
         _require_device()
-        w = _f32(wave)
+        w = _c(wave)
         B, L = w.shape
         nb = n_fft // 2 + 1
         if wr.numel() != nb * n_fft or wi.numel() != nb * n_fft:
             raise ValueError(f"CustomSTFT: forward bases {tuple(wr.shape)} / {tuple(wi.shape)} for n_fft {n_fft}")
         out = torch.empty(B, L // hop + 1, n_fft + 2, dtype=torch.float32, device=w.device)
-        check(lib().stts_cstft_fwd(_ptr(w), _ptr(_f32(wr)), _ptr(_f32(wi)), B, L, n_fft, hop, _ptr(out), _stream()),
-              "stts_cstft_fwd")
+        call("stts_cstft_fwd", w, _c(wr), _c(wi), B, L, n_fft, hop, out)
         ctx.mark_non_differentiable(out)
         return out
 
@@ -1315,9 +1251,9 @@ class _PadLAddFn(torch.autograd.Function):
         B, L, C = x.shape
         if tuple(src.shape) != (B, L + 1, C):
             raise ValueError(f"padl_add: x {tuple(x.shape)}, src {tuple(src.shape)}: expected {(B, L + 1, C)}")
-        xc, sc = _f32(x), _f32(src)
+        xc, sc = _c(x), _c(src)
         y = torch.empty_like(sc)
-        check(lib().stts_padl_add_fwd(_ptr(xc), _ptr(sc), B, L, C, _ptr(y), _stream()), "stts_padl_add_fwd")
+        call("stts_padl_add_fwd", xc, sc, B, L, C, y)
         ctx.shape = (B, L, C)
         return y
 
@@ -1327,9 +1263,9 @@ class _PadLAddFn(torch.autograd.Function):
         nx, ns = ctx.needs_input_grad
         dx = None
         if nx:
-            dy = _f32(gy)
+            dy = _c(gy)
             dx = torch.empty(B, L, C, dtype=torch.float32, device=dy.device)
-            check(lib().stts_padl_add_bwd(_ptr(dy), B, L, C, _ptr(dx), _stream()), "stts_padl_add_bwd")
+            call("stts_padl_add_bwd", dy, B, L, C, dx)
         return dx, (gy if ns else None)  # dx is its own tensor (see _SumDivFn.backward); src's gradient is dy itself
 
 
@@ -1349,10 +1285,9 @@ class _CISTFTHeadFn(torch.autograd.Function):
         if W != 2 * nb or br.numel() != nb * n_fft or bi.numel() != nb * n_fft:
             raise ValueError(f"CustomSTFT head: post {tuple(post.shape)}, bases {tuple(br.shape)} / {tuple(bi.shape)} "
                              f"for n_fft {n_fft}")
-        pc, brc, bic = _f32(post), _f32(br), _f32(bi)
+        pc, brc, bic = _c(post), _c(br), _c(bi)
         y = torch.empty(B, max(F - 1, 0) * hop, dtype=torch.float32, device=pc.device)
-        check(lib().stts_cistft_head_fwd(_ptr(pc), _ptr(brc), _ptr(bic), B, F, n_fft, hop, _ptr(y), _stream()),
-              "stts_cistft_head_fwd")
+        call("stts_cistft_head_fwd", pc, brc, bic, B, F, n_fft, hop, y)
         ctx.save_for_backward(pc, brc, bic)
         ctx.geo = (n_fft, hop)
         return y
@@ -1362,10 +1297,9 @@ class _CISTFTHeadFn(torch.autograd.Function):
         pc, brc, bic = ctx.saved_tensors
         n_fft, hop = ctx.geo
         B, F, _ = pc.shape
-        dy = _f32(gy)
+        dy = _c(gy)
         dp = torch.empty_like(pc)
-        check(lib().stts_cistft_head_bwd(_ptr(pc), _ptr(brc), _ptr(bic), _ptr(dy), B, F, n_fft, hop, _ptr(dp),
-                                         _stream()), "stts_cistft_head_bwd")
+        call("stts_cistft_head_bwd", pc, brc, bic, dy, B, F, n_fft, hop, dp)
         return dp, None, None, None, None
 
 
@@ -1514,8 +1448,7 @@ class _DropoutFn(torch.autograd.Function):
         xc = _c(x)
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         y = torch.empty_like(xc)
-        check(lib().stts_dropout(_ptr(xc), xc.numel(), ctypes.c_float(p), ctypes.c_ulonglong(seed), _ptr(y),
-                                 _stream()), "stts_dropout")
+        call("stts_dropout", xc, xc.numel(), p, seed, y)
         ctx.p, ctx.seed = p, seed
         return y
 
@@ -1523,8 +1456,7 @@ class _DropoutFn(torch.autograd.Function):
     def backward(ctx, dy):
         dyc = _c(dy)
         dx = torch.empty_like(dyc)
-        check(lib().stts_dropout(_ptr(dyc), dyc.numel(), ctypes.c_float(ctx.p), ctypes.c_ulonglong(ctx.seed),
-                                 _ptr(dx), _stream()), "stts_dropout")
+        call("stts_dropout", dyc, dyc.numel(), ctx.p, ctx.seed, dx)
         return dx, None
 
 
@@ -1538,8 +1470,7 @@ class _DropoutMaskFn(torch.autograd.Function):
         if mc.shape != xc.shape:
             raise ValueError(f"dropout mask {tuple(mc.shape)} for a tensor {tuple(xc.shape)}")
         y = torch.empty_like(xc)
-        check(lib().stts_dropout_mask(_ptr(xc), _ptr(mc), xc.numel(), ctypes.c_float(p), _ptr(y), _stream()),
-              "stts_dropout_mask")
+        call("stts_dropout_mask", xc, mc, xc.numel(), p, y)
         ctx.save_for_backward(mc)
         ctx.p = p
         return y
@@ -1549,8 +1480,7 @@ class _DropoutMaskFn(torch.autograd.Function):
         (mc,) = ctx.saved_tensors
         dyc = _c(dy)
         dx = torch.empty_like(dyc)
-        check(lib().stts_dropout_mask(_ptr(dyc), _ptr(mc), dyc.numel(), ctypes.c_float(ctx.p), _ptr(dx), _stream()),
-              "stts_dropout_mask")
+        call("stts_dropout_mask", dyc, mc, dyc.numel(), ctx.p, dx)
         return dx, None, None
 
 
@@ -1595,12 +1525,10 @@ class _BiLSTMFn(torch.autograd.Function):
         ps = [_c(p) for p in params]
         H = ps[1].shape[1]
         arr = (ctypes.c_void_p * 8)(*[p.data_ptr() for p in ps])
-        L = lib()
-        ws, nb = _workspace("stts_bilstm_workspace_bytes", x.device, B, T, H)
         y = torch.empty(B, T, 2 * H, dtype=torch.float32, device=x.device)
         cs = torch.empty(2, B, T, H, dtype=torch.float32, device=x.device)
-        check(L.stts_bilstm_fwd_train(_ptr(xc), T * Cin, Cin, 1, B, T, Cin, _ptr(ln), arr, H, _ptr(y), _ptr(cs),
-                                      _ptr(ws), nb, _stream()), "stts_bilstm_fwd_train")
+        call("stts_bilstm_fwd_train", xc, T * Cin, Cin, 1, B, T, Cin, ln, arr, H, y, cs,
+             ws=("stts_bilstm_workspace_bytes", B, T, H))
         ctx.save_for_backward(xc, y, cs, ln if ln is not None else torch.empty(0), *ps)
         ctx.has_ln = ln is not None
         return y
@@ -1617,10 +1545,8 @@ class _BiLSTMFn(torch.autograd.Function):
         grads = [torch.empty_like(p) if need[i + 2] else None for i, p in enumerate(ps)]
         arr = (ctypes.c_void_p * 8)(*[p.data_ptr() for p in ps])
         garr = (ctypes.c_void_p * 8)(*[g.data_ptr() if g is not None else None for g in grads])
-        L = lib()
-        ws, nb = _workspace("stts_bilstm_bwd_workspace_bytes", dy.device, B, T, Cin, H)
-        check(L.stts_bilstm_bwd(_ptr(xc), B, T, Cin, _ptr(ln), arr, H, _ptr(y), _ptr(cs), _ptr(dyc), _ptr(dx), garr,
-                                _ptr(ws), nb, _stream()), "stts_bilstm_bwd")
+        call("stts_bilstm_bwd", xc, B, T, Cin, ln, arr, H, y, cs, dyc, dx, garr,
+             ws=("stts_bilstm_bwd_workspace_bytes", B, T, Cin, H))
         return (dx, None, *grads)
 
 
@@ -1657,7 +1583,7 @@ class _RowExpFn(torch.autograd.Function):
         B, H, W, C = xc.shape
         Ho = H + 2 * pad - k + 1
         xe = torch.empty(B, Ho, W, C * k, dtype=torch.float32, device=x.device)
-        check(lib().stts_rowexp_fwd(_ptr(xc), B, H, W, C, k, pad, _ptr(xe), _stream()), "stts_rowexp_fwd")
+        call("stts_rowexp_fwd", xc, B, H, W, C, k, pad, xe)
         ctx.geom = (B, H, W, C, k, pad)
         return xe
 
@@ -1666,7 +1592,7 @@ class _RowExpFn(torch.autograd.Function):
         B, H, W, C, k, pad = ctx.geom
         d = _c(dxe)
         dx = torch.empty(B, H, W, C, dtype=torch.float32, device=d.device)
-        check(lib().stts_rowexp_bwd(_ptr(d), B, H, W, C, k, pad, _ptr(dx), _stream()), "stts_rowexp_bwd")
+        call("stts_rowexp_bwd", d, B, H, W, C, k, pad, dx)
         return dx, None, None
 
 
@@ -1679,8 +1605,7 @@ class _DWConvS2Fn(torch.autograd.Function):
         xc, wc, bc = _c(x), _c(w), _c(b)
         B, H, W, C = xc.shape
         y = torch.empty(B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C, dtype=torch.float32, device=x.device)
-        check(lib().stts_dwconv2d_s2_fwd(_ptr(xc), _ptr(wc), _ptr(bc), B, H, W, C, _ptr(y), _stream()),
-              "stts_dwconv2d_s2_fwd")
+        call("stts_dwconv2d_s2_fwd", xc, wc, bc, B, H, W, C, y)
         ctx.save_for_backward(xc, wc)
         ctx.has_b = b is not None
         return y
@@ -1690,14 +1615,11 @@ class _DWConvS2Fn(torch.autograd.Function):
         xc, wc = ctx.saved_tensors
         B, H, W, C = xc.shape
         d = _c(dy)
-        nx, nw, nb_ = ctx.needs_input_grad
+        nx, nw, nb = ctx.needs_input_grad
         dx = torch.empty_like(xc) if nx else None
         dw = torch.empty_like(wc) if nw else None
-        db = torch.empty(C, dtype=torch.float32, device=d.device) if (nb_ and ctx.has_b) else None
-        L = lib()
-        ws, nb = _workspace("stts_dwconv2d_s2_workspace_bytes", d.device, C)
-        check(L.stts_dwconv2d_s2_bwd(_ptr(xc), _ptr(wc), _ptr(d), B, H, W, C, _ptr(dx), _ptr(dw), _ptr(db), _ptr(ws), nb,
-                                     _stream()), "stts_dwconv2d_s2_bwd")
+        db = torch.empty(C, dtype=torch.float32, device=d.device) if (nb and ctx.has_b) else None
+        call("stts_dwconv2d_s2_bwd", xc, wc, d, B, H, W, C, dx, dw, db, ws=("stts_dwconv2d_s2_workspace_bytes", C))
         return dx, dw, db
 
 
@@ -1710,7 +1632,7 @@ class _AvgPool2Fn(torch.autograd.Function):
         xc = _c(x)
         B, H, W, C = xc.shape
         y = torch.empty(B, H // 2, (W + 1) // 2, C, dtype=torch.float32, device=x.device)
-        check(lib().stts_avgpool2_fwd(_ptr(xc), B, H, W, C, _ptr(y), _stream()), "stts_avgpool2_fwd")
+        call("stts_avgpool2_fwd", xc, B, H, W, C, y)
         ctx.geom = (B, H, W, C)
         return y
 
@@ -1719,7 +1641,7 @@ class _AvgPool2Fn(torch.autograd.Function):
         B, H, W, C = ctx.geom
         d = _c(dy)
         dx = torch.empty(B, H, W, C, dtype=torch.float32, device=d.device)
-        check(lib().stts_avgpool2_bwd(_ptr(d), B, H, W, C, _ptr(dx), _stream()), "stts_avgpool2_bwd")
+        call("stts_avgpool2_bwd", d, B, H, W, C, dx)
         return dx
 
 
@@ -1732,7 +1654,7 @@ class _SpatialMeanFn(torch.autograd.Function):
         xc = _c(x)
         B, H, W, C = xc.shape
         y = torch.empty(B, C, dtype=torch.float32, device=x.device)
-        check(lib().stts_spatial_mean_fwd(_ptr(xc), B, H * W, C, _ptr(y), _stream()), "stts_spatial_mean_fwd")
+        call("stts_spatial_mean_fwd", xc, B, H * W, C, y)
         ctx.geom = (B, H, W, C)
         return y
 
@@ -1741,7 +1663,7 @@ class _SpatialMeanFn(torch.autograd.Function):
         B, H, W, C = ctx.geom
         d = _c(dy)
         dx = torch.empty(B, H, W, C, dtype=torch.float32, device=d.device)
-        check(lib().stts_spatial_mean_bwd(_ptr(d), B, H * W, C, _ptr(dx), _stream()), "stts_spatial_mean_bwd")
+        call("stts_spatial_mean_bwd", d, B, H * W, C, dx)
         return dx
 
 

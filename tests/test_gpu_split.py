@@ -19,16 +19,13 @@ SPLIT = 2  # STTS_SPLIT
 
 def _conv_split(x, w, b, stride, pad, dil, dtype=SPLIT):
     """stts_conv1d_fwd on frames x [B, Lin, Cin] -> [B, Lq, Cout] (fp32 tensors on the device)."""
-    from stts2_mi355x.engine import _ptr, _stream, check, lib
+    from stts2_mi355x.engine import call
     B, Lin, Cin = x.shape
     Cout, _, K = w.shape
     Lq = (Lin + 2 * pad - dil * (K - 1) - 1) // stride + 1
-    nb = lib().stts_conv1d_fwd_workspace_bytes(dtype, B, Lin, Cin, Cout, K, stride, dil, pad, Lq)
-    check(int(nb) if nb < 0 else 0, "stts_conv1d_fwd_workspace_bytes")
-    ws = torch.empty(max(int(nb), 1), dtype=torch.uint8, device="cuda")
     y = torch.empty(B, Lq, Cout, device="cuda")
-    check(lib().stts_conv1d_fwd(dtype, _ptr(x), _ptr(w), _ptr(b), B, Lin, Cin, Cout, K, stride, dil, pad, Lq, _ptr(y),
-                                _ptr(ws), int(nb), _stream()), "stts_conv1d_fwd")
+    call("stts_conv1d_fwd", dtype, x, w, b, B, Lin, Cin, Cout, K, stride, dil, pad, Lq, y,
+         ws=("stts_conv1d_fwd_workspace_bytes", dtype, B, Lin, Cin, Cout, K, stride, dil, pad, Lq))
     torch.cuda.synchronize()
     return y
 

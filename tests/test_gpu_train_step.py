@@ -120,6 +120,34 @@ def test_snake_tanh_sum():
     assert all(torch.allclose(v.grad, torch.full_like(v, 1 / 3)) for v in xs)
 
 
+def test_native_calls_run_on_the_current_side_stream():
+    """engine.call appends torch's *current* stream: inside torch.cuda.stream(side), _TanhFn's forward and backward
+    read an input that `side` writes only after a few ms of queued work, so a launch on a stream not ordered after
+    `side` would read the zeros the tensor held before (the null stream does order itself after `side` on this
+    runtime: substituting it still passes).  Bar 1e-6 absolute against fp64: |tanh| < 1 and 0 < tanh' <= 1, a few fp32 ulps
+    (6e-8 each) of tanhf, and 2 |y| times that again for 1 - y^2."""
+    from stts2_mi355x import training as T
+    vals = torch.tensor([-1.5, 0.25, 3.0])
+    vals_d = vals.cuda()
+    side = torch.cuda.Stream()
+    x = torch.zeros(3, device="cuda")
+    busy = torch.zeros(1 << 26, device="cuda")
+    torch.cuda.synchronize()
+    with torch.cuda.stream(side):
+        for _ in range(40):
+            busy.add_(1.0)
+        x.copy_(vals_d)  # (device to device: the host does not wait for `side` here)
+        xg = x.requires_grad_(True)
+        y = T.tanh(xg)
+        y.sum().backward()
+    side.synchronize()
+    ref = vals.double().requires_grad_(True)
+    yr = torch.tanh(ref)
+    yr.sum().backward()
+    assert (y.detach().cpu().double() - yr.detach()).abs().max() < 1e-6
+    assert (xg.grad.cpu().double() - ref.grad).abs().max() < 1e-6
+
+
 @pytest.mark.parametrize("k", [3, 7, 15])
 def test_box_smooth(k):
     from stts2_mi355x import training as T

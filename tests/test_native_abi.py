@@ -453,3 +453,66 @@ def test_bilstm_error_word_offset():
         off = L.stts_bilstm_error_offset(B, T, H)
         assert 0 < off and off % 8 == 0 and off + 8 <= L.stts_bilstm_workspace_bytes(B, T, H)
     assert L.stts_bilstm_error_offset(-1, 1, 1) < 0
+
+
+# ---------------------------------------------------------------------- engine.call / engine.query
+def test_stream_is_the_last_parameter_wherever_it_appears():
+    """engine.call appends the current stream when the caller leaves one argument out: sound only if every prototype
+    with a parameter named `stream` has it last."""
+    seen = set()
+    for fname, src in _headers().items():
+        src = re.sub(r"^\s*#.*$", "", src, flags=re.M)
+        for name, params in re.findall(r"\b(stts_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+            names = [re.split(r"[\s\*]+", p.strip())[-1] for p in params.split(",")]
+            if "stream" in names:
+                seen.add(name)
+                assert names.index("stream") == len(names) - 1 and names.count("stream") == 1, f"{fname}: {name}"
+                assert E.SIGNATURES[name][0][-1] is ctypes.c_void_p, name
+    assert {"stts_decoder_fwd", "stts_linear_fwd", "stts_snake_bwd", "stts_adamw_step"} <= seen  # the parser sees them
+
+
+def test_size_query_through_the_helper():
+    assert E.query("stts_snake_workspace_bytes", 2, 3, 4) == E.lib().stts_snake_workspace_bytes(2, 3, 4) > 0
+
+
+def test_invalid_size_query_raises_with_its_name():
+    with pytest.raises(RuntimeError, match="stts_snake_workspace_bytes failed: .* \\(code -\\d+\\)"):
+        E.query("stts_snake_workspace_bytes", 0, 3, 4)
+    with pytest.raises(TypeError, match="stts_snake_workspace_bytes"):  # a query is no status: no stream to append
+        E.call("stts_snake_workspace_bytes", 2, 3)
+
+
+def test_call_refuses_a_wrong_argument_count_before_anything_runs():
+    """Two arguments too few and one too many name the entry and both counts; they raise before the stream lookup
+    (which needs a device), as does one too few for an entry that takes no stream."""
+    n = len(E.SIGNATURES["stts_linear_fwd"][0])
+    with pytest.raises(TypeError, match=f"stts_linear_fwd takes {n} arguments.*got {n - 2}"):
+        E.call("stts_linear_fwd", *([None] * (n - 2)))
+    with pytest.raises(TypeError, match=f"stts_linear_fwd takes {n} arguments.*got {n + 1}"):
+        E.call("stts_linear_fwd", *([None] * (n + 1)))
+    with pytest.raises(TypeError, match="stts_snake_bwd takes 11 arguments.*got 9 \\+ workspace"):
+        E.call("stts_snake_bwd", *([None] * 9), ws=("stts_snake_workspace_bytes", 2, 3, 4))
+    with pytest.raises(TypeError, match="stts_set_option takes 2 arguments, got 1"):
+        E.call("stts_set_option", 1)
+
+
+def test_call_converts_tensors_at_the_pointer_positions_only():
+    """The converter of stts_linear_fwd against a stub in the library function's place: data_ptr() ints at exactly
+    the c_void_p positions of its signature, None untouched (ctypes' NULL), the three ints and an explicit stream as
+    given; the stub's status raises in check()'s format."""
+    args_t = E.SIGNATURES["stts_linear_fwd"][0]
+    assert [t is ctypes.c_void_p for t in args_t] == [True, True, True, False, False, False, True, True]
+    got = []
+
+    def stub(*a):
+        got.append(a)
+        return 0
+
+    s, W, h = torch.zeros(2, 3), torch.zeros(4, 3), torch.zeros(2, 4)
+    cached = E._ENTRIES.get("stts_linear_fwd")
+    E._bind("stts_linear_fwd", stub)((s, W, None, 2, 3, 4, h, 0))
+    assert got == [(s.data_ptr(), W.data_ptr(), None, 2, 3, 4, h.data_ptr(), 0)]
+    assert all(type(v) is int for v in got[0] if v is not None)
+    assert E._ENTRIES.get("stts_linear_fwd") is cached  # a stub's converter does not replace the library's
+    with pytest.raises(RuntimeError, match="^stts_linear_fwd failed: .* \\(code -1\\)$"):
+        E._bind("stts_linear_fwd", lambda *a: -1)((s, W, None, 2, 3, 4, h, 0))

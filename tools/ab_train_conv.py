@@ -68,14 +68,11 @@ def main():
             E.set_option(a.opt, v)
             res = {"shape": name, "opt": a.opt, "value": v}
             calls = {
-                "fwd": lambda: E.check(L.stts_conv1d_fwd(dt, E._ptr(x), E._ptr(w), E._ptr(bias), B, Lin, Cin, Cout, K,
-                                                         s, d, p, Lq, E._ptr(y), E._ptr(ws), nb, E._stream()), "fwd"),
-                "dx": lambda: E.check(L.stts_conv1d_bwd(dt, E._ptr(x), E._ptr(w), E._ptr(dy), B, Lin, Cin, Cout, K, s,
-                                                        d, p, Lq, E._ptr(dx), None, None, E._ptr(ws), nb,
-                                                        E._stream()), "dx"),
-                "dw": lambda: E.check(L.stts_conv1d_bwd(dt, E._ptr(x), E._ptr(w), E._ptr(dy), B, Lin, Cin, Cout, K, s,
-                                                        d, p, Lq, None, E._ptr(dw), None, E._ptr(ws), nb,
-                                                        E._stream()), "dw"),
+                "fwd": lambda: E.call("stts_conv1d_fwd", dt, x, w, bias, B, Lin, Cin, Cout, K, s, d, p, Lq, y, ws, nb),
+                "dx": lambda: E.call("stts_conv1d_bwd", dt, x, w, dy, B, Lin, Cin, Cout, K, s, d, p, Lq, dx, None, None,
+                                     ws, nb),
+                "dw": lambda: E.call("stts_conv1d_bwd", dt, x, w, dy, B, Lin, Cin, Cout, K, s, d, p, Lq, None, dw, None,
+                                     ws, nb),
             }
             for tag, fn in calls.items():
                 ms = timed(fn)

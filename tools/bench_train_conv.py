@@ -41,9 +41,8 @@ def main():
                     continue  # dw is fp32 in both modes
 
                 def call():
-                    E.check(L.stts_conv1d_bwd(dt, E._ptr(x), E._ptr(w), E._ptr(dy), B, Lin, Cin, Cout, K, s, d, p,
-                                              Lq, E._ptr(args[0]), E._ptr(args[1]), None, E._ptr(ws), nb,
-                                              E._stream()), "bwd")
+                    E.call("stts_conv1d_bwd", dt, x, w, dy, B, Lin, Cin, Cout, K, s, d, p, Lq, args[0], args[1], None,
+                           ws, nb)
                 for _ in range(3):
                     call()
                 a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

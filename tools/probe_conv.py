@@ -1,5 +1,4 @@
 """Probe: return codes of the conv engine test hook vs stts_conv1d_fwd for a few shapes."""
-import ctypes
 import sys
 
 import torch
@@ -18,13 +17,12 @@ for (B, Cin, Cout, K, s, d, p, Lin) in [(2, 1090, 1024, 3, 1, 1, 1, 40), (2, 109
     for dt in (0, 1):
         for pm in (0, 5):
             gb = torch.ones(B, 2 * Cin, device="cuda")
-            rc = L.stts_test_conv1d(dt, E._ptr(x), B, Lin, Cin, E._ptr(w), None, Cout, K, 0, s, d, p, 0, pm,
-                                    E._ptr(gb), None, ctypes.c_float(0.2), None, ctypes.c_float(1.0), E._ptr(y),
-                                    Lq, None)
+            rc = L.stts_test_conv1d(dt, x.data_ptr(), B, Lin, Cin, w.data_ptr(), None, Cout, K, 0, s, d, p, 0, pm,
+                                    gb.data_ptr(), None, 0.2, None, 1.0, y.data_ptr(), Lq, None)
             print("test hook", (B, Cin, Cout, K, s, d, p, Lin), "dt", dt, "pro", pm, "rc", rc, flush=True)
         nb = L.stts_conv1d_fwd_workspace_bytes(dt, B, Lin, Cin, Cout, K, s, d, p, Lq)
         ws = torch.empty(nb, dtype=torch.uint8, device="cuda")
-        rc = L.stts_conv1d_fwd(dt, E._ptr(x), E._ptr(w), None, B, Lin, Cin, Cout, K, s, d, p, Lq, E._ptr(y),
-                               E._ptr(ws), nb, E._stream())
+        rc = L.stts_conv1d_fwd(dt, x.data_ptr(), w.data_ptr(), None, B, Lin, Cin, Cout, K, s, d, p, Lq, y.data_ptr(),
+                               ws.data_ptr(), nb, E._stream())
         print("fwd", (B, Cin, Cout, K, s, d, p, Lin), "dt", dt, "rc", rc, flush=True)
 torch.cuda.synchronize()
