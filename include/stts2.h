@@ -44,6 +44,8 @@ typedef struct stts_model stts_model;
 #define STTS_KIND_PITCH 8    /* Modules/JDC/model.py JDCNet (the frozen pitch extractor of the training step);
                                 cfg = {num_class}, the reference's {1}.  (7 stays an unknown kind: the ABI
                                 tests pin it as the rejected example.) */
+#define STTS_KIND_ALIGNER 9  /* Modules/ASR/models.py ASRCNN (the text aligner of the training step); cfg =
+                                {input_dim (80), hidden_dim (256), n_token, n_layers, token_embedding_dim} */
 
 /* compute / activation dtypes */
 #define STTS_FP32 0 /* fp32 storage, exact-fp32 MFMA (parity mode)          */
@@ -86,7 +88,8 @@ long long stts_packed_bytes(const stts_model* m, int dtype);
 int stts_pack(stts_model* m, int dtype, void* packed, long long bytes, void* stream);
 
 /* Workspace for one forward of B utterances of T frames (decoder: T = asr frames;
- * F0N: T = text-aligned frames; STYLE, PITCH: T = mel frames). */
+ * F0N: T = text-aligned frames; STYLE, PITCH, ALIGNER: T = mel frames; for the aligner this sizes a forward
+ * without tokens, stts_aligner_workspace_bytes one with them). */
 long long stts_workspace_bytes(const stts_model* m, int dtype, int B, int T);
 
 /* Decoder: asr [B][dim_in][T], F0_curve [B][2T], N [B][2T], s [B][style_dim] -> out [B][1][600T]
@@ -121,6 +124,34 @@ long long stts_pitch_error_offset(const stts_model* m, int dtype, int B, int T);
 /* utils.py:48-53 log_norm(x, mean, std, dim = the mel axis): mel [B][n_mels][T] -> out [B][T] =
  * log(|| exp(x * std + mean) ||_2 over the n_mels bins), fp32 expf / logf, bins summed in a fixed order. */
 int stts_log_norm(const float* mel, int B, int n_mels, int T, float mean, float std, float* out, void* stream);
+
+/* Text aligner, <- Modules/ASR/models.py:37-48 ASRCNN.forward in eval mode (train.py:206, validation :381):
+ * mel [B][80][T] -> ctc [B][L][n_token], L = ceil(T / 2), and feature [B][128][L] (get_feature, :50-55).  With
+ * tokens (int [B][Tt], Tt >= 1) also the S2S decoder over Tt + 1 steps (the SOS step first): s2s_logit
+ * [B][Tt + 1][n_token] and attn [B][Tt + 1][L].  pad_mask: bytes [B][L], non-zero = padded frame (-inf before the
+ * softmax; only the attention reads it, the CNN sees the zero-padded batch as it is), or NULL.  unk_mask: bytes
+ * [B][Tt], non-zero = that token is replaced by the unknown index 3 (models.py:126-128 draws it in eval mode too; the
+ * caller draws), or NULL.  Token indices outside [0, n_token) are the caller's to refuse.  A NULL output pointer
+ * skips that output; without tokens only ctc / feature are produced.  dtype: STTS_FP32 or STTS_SPLIT (the convs'
+ * dtype; GroupNorm, the products around the recurrence and the recurrence itself are always fp32); STTS_BF16 returns
+ * STTS_EDTYPE.  L <= 4096.  The decoder loop is one launch of one workgroup per utterance: no workgroup waits for
+ * another, so there is no time-out and no error word.  Workspace: stts_aligner_workspace_bytes(m, dtype, B, T, Tt),
+ * Tt = 0 without tokens. */
+int stts_aligner_fwd(stts_model* m, int dtype, const float* mel, const unsigned char* pad_mask, const int* tokens,
+                     const unsigned char* unk_mask, int B, int T, int Tt, float* ctc, float* s2s_logit, float* attn,
+                     float* feature, void* workspace, long long ws_bytes, void* stream);
+long long stts_aligner_workspace_bytes(const stts_model* m, int dtype, int B, int T, int Tt);
+
+/* Monotonic alignment search, <- utils.py:14-27 maximum_path (the Glow-TTS search monotonic_align packages), fp32:
+ * value [B][Tx][Ty] (device) and, per utterance, tx_len rows (tokens) and ty_len columns (frames), HOST int arrays
+ * [B] -> path [B][Tx][Ty] (device, fp32 0 / 1; everything outside [0, tx) x [0, ty) is 0).  Forward, for y in
+ * 0..ty-1 and x in max(0, tx + y - ty) .. min(tx, y + 1) - 1: v[x][y] += max(x == 0 ? (y == 0 ? 0 : -1e9) :
+ * v[x-1][y-1], x == y ? -1e9 : v[x][y-1]); backtrack from idx = tx - 1 for y = ty-1 .. 0: path[idx][y] = 1, then
+ * idx -= 1 when idx != 0 and (idx == y or v[idx][y-1] < v[idx-1][y-1]).  1 <= tx_len <= ty_len <= Ty, tx_len <= Tx
+ * <= 4096, or STTS_EINVAL: the search is undefined elsewhere. */
+long long stts_maximum_path_workspace_bytes(int B, int Tx, int Ty);
+int stts_maximum_path(const float* value, const int* tx_len, const int* ty_len, int B, int Tx, int Ty, float* path,
+                      void* workspace, long long ws_bytes, void* stream);
 
 /* MultiPeriodDiscriminator forward, <- Modules/discriminators.py:108-129 DiscriminatorP.forward for
  * every period (MultiPeriodDiscriminator.forward :143-156 calls it on y and y_hat: pass both as one

@@ -304,6 +304,38 @@ int st_bilstm_fwd(const float* x, long long xs_b, long long xs_t, long long xs_c
                   const int* lengths, const float* const* params, int H, float* y, float* h_n, float* c_n,
                   void* workspace, long long ws_bytes, int splitk, hipStream_t s);
 
+// ---------------------------------------------------------------- text aligner (aligner.hip, ASRCNN + the search)
+// All fp32, every sum in a fixed order, no atomics.
+constexpr int ST_ALIGNER_MAX_L = 4096;   // memory frames one decoder workgroup keeps weights for in LDS
+constexpr int ST_MAXPATH_MAX_TX = 4096;  // tokens whose two search columns fit LDS
+// mel [B][nm][T] -> frames [B][T][ld]: channel c < nc = sum_m mel[m] dct[m][c] (m in order), channels [nc, ld) zero
+int st_mfcc_frames(const float* mel, const float* dct, int B, int nm, int T, int nc, int ld, float* dst, hipStream_t s);
+// GroupNorm(G) over frames [B][L][ld] (channels [0, C)), of ReLU(x) when relu: statistics per (utterance, group) over
+// the group's channels x all L frames, biased variance; y may be x
+int st_groupnorm(const float* x, int B, int L, int ld, int C, int G, int relu, const float* w, const float* b, float eps,
+                 float* y, hipStream_t s);
+int st_add(float* x, const float* r, long long n, hipStream_t s);  // x += r
+int st_frames_to_ncl(const float* x, int B, int L, int C, float* out, hipStream_t s);
+// dst[c][r] = src[r ld + c0 + c], r < rows, c < cols (pack time)
+int st_transpose(const float* src, int rows, int cols, int ld, int c0, float* dst, hipStream_t s);
+// C[r][n] = act(bias[n] + bias2[n] + sum_k A[r][k] W[n][k]) (k ascending; biases may be null; act 0 none, 1 ReLU,
+// 2 tanh)
+int st_gemm_nt(const float* A, long long rows, int K, int lda, const float* W, int N, int ldw, const float* bias,
+               const float* bias2, int act, float* C, int ldc, hipStream_t s);
+// ASRS2S decoder inputs [B][Tt + 1][E]: the SOS row (index 1), then the tokens' rows (index 3 where unk_mask is set)
+int st_s2s_embed(const int* tok, const unsigned char* unk_mask, int B, int Tt, int E, int ntok, const float* emb,
+                 float* out, hipStream_t s);
+// ASRS2S.decode for `steps` steps, one persistent workgroup per utterance: gin [B][steps][512] (the hoisted input part
+// of the gates with both biases), wc_t [256][512], wq_t [128][128], wloc_t [126][32] (k-major), wd [128][32], v [128],
+// mem / pmem [B][L][128], mask bytes [B][L] or null -> attn [B][steps][L] (may be null), hc [B][steps][h; context]
+int st_s2s_decode(const float* gin, const float* wc_t, const float* wq_t, const float* wloc_t, const float* wd,
+                  const float* v, const float* mem, const float* pmem, const unsigned char* mask, int B, int L, int steps,
+                  float* attn, float* hc, hipStream_t s);
+// monotonic alignment search: value [B][Tx][Ty], HOST lengths -> path [B][Tx][Ty] of 0 / 1
+long long st_max_path_workspace_bytes(int B, int Tx, int Ty);
+int st_max_path(const float* value, const int* tx_len, const int* ty_len, int B, int Tx, int Ty, float* path, void* ws,
+                long long ws_bytes, hipStream_t s);
+
 // ---------------------------------------------------------------- training-step spectra (spec.hip)
 long long st_stft_frames(long long L, int hop);
 // torchaudio MelSpectrogram(sr, n_fft, win, hop, hann, n_mels) -> (log(1e-5 + mel) + 4) / 4:

@@ -250,6 +250,22 @@ struct stts_model {
   BNorm pe_bn0, pe_pool;
   int pe_lstm[8] = {-1, -1, -1, -1, -1, -1, -1, -1}, pe_cls_w = -1, pe_cls_b = -1, pe_nclass = 0;
   std::vector<BNorm*> bns;
+  // -------- text aligner (Modules/ASR/models.py ASRCNN; forward :37-48, ASRS2S :118-176)
+  struct ALBlk {  // one entry of ConvBlock.blocks: conv(dil) -> ReLU -> GroupNorm(8) -> conv -> ReLU, + input
+    WConv c1, c2;
+    int dil = 1, gn_w = -1, gn_b = -1;
+  };
+  struct ALLayer {  // ConvBlock, GroupNorm(1)
+    ALBlk blk[3];
+    int gn_w = -1, gn_b = -1;
+  };
+  std::vector<ALLayer> al_layers;
+  WConv al_init, al_proj;
+  int al_ntok = 0, al_emb = 0;
+  int al_dct = -1, al_ctc_w[2] = {-1, -1}, al_ctc_b[2] = {-1, -1}, al_embw = -1, al_pns_w = -1, al_pns_b = -1,
+      al_query = -1, al_memory = -1, al_v = -1, al_loc = -1, al_dense = -1, al_wih = -1, al_whh = -1, al_bih = -1,
+      al_bhh = -1, al_ph_w = -1, al_ph_b = -1;
+  size_t al_wc_t = 0, al_wq_t = 0, al_wloc_t = 0;  // aux: the recurrence's weights k-major (pack_model)
   // -------- AdaIN projections (all AdaIN layers share one GEMV: H = s @ Wt + b)
   std::vector<WAdaIN*> adains;
   int Htot = 0;
@@ -558,6 +574,57 @@ int build_pitch(Model& m, const int* cfg, int n) {
   return ST_OK;
 }
 
+// ASRCNN(input_dim, hidden_dim, n_token, n_layers, token_embedding_dim) (Modules/ASR/models.py:9-35): every one of
+// its 143 state-dict entries is read by forward, so the plan's names are the state dict's.  The kernels are built for
+// the reference's widths: 80 mel bins -> 40 MFCCs, hidden_dim 256 (memory, decoder and attention width 128).
+constexpr int kAlMel = 80, kAlMfcc = 40, kAlHid = 256, kAlDec = 128, kAlLocF = 32, kAlLocK = 63;
+int build_aligner(Model& m, const int* cfg, int n) {
+  if (n != 5 || cfg[0] != kAlMel || cfg[1] != kAlHid || cfg[2] < 4 || cfg[3] < 1 || cfg[3] > 64 || cfg[4] < 1)
+    return ST_EINVAL;
+  m.al_ntok = cfg[2];
+  m.al_emb = cfg[4];
+  const int H = kAlHid, D = kAlDec;
+  m.al_dct = m.P.add("to_mfcc.dct_mat", (long long)kAlMel * kAlMfcc);
+  add_wconv(m, m.al_init, "init_cnn.conv", kAlMfcc, H, 7, false, true);
+  m.al_layers.resize(cfg[3]);  // sized once: add_wconv keeps pointers into it
+  for (int i = 0; i < cfg[3]; ++i) {
+    auto& l = m.al_layers[i];
+    const std::string p = "cnns." + std::to_string(i);
+    for (int j = 0, dil = 1; j < 3; ++j, dil *= 3) {
+      auto& b = l.blk[j];
+      const std::string q = p + ".0.blocks." + std::to_string(j);
+      b.dil = dil;
+      add_wconv(m, b.c1, q + ".0.conv", H, H, 3, false, true);
+      b.gn_w = m.P.add(q + ".2.weight", H);
+      b.gn_b = m.P.add(q + ".2.bias", H);
+      add_wconv(m, b.c2, q + ".4.conv", H, H, 3, false, true);
+    }
+    l.gn_w = m.P.add(p + ".1.weight", H);
+    l.gn_b = m.P.add(p + ".1.bias", H);
+  }
+  add_wconv(m, m.al_proj, "projection.conv", H, D, 1, false, true);
+  m.al_ctc_w[0] = m.P.add("ctc_linear.0.linear_layer.weight", (long long)H * D);
+  m.al_ctc_b[0] = m.P.add("ctc_linear.0.linear_layer.bias", H);
+  m.al_ctc_w[1] = m.P.add("ctc_linear.2.linear_layer.weight", (long long)m.al_ntok * H);
+  m.al_ctc_b[1] = m.P.add("ctc_linear.2.linear_layer.bias", m.al_ntok);
+  const std::string s = "asr_s2s.", a = s + "attention_layer.";
+  m.al_embw = m.P.add(s + "embedding.weight", (long long)m.al_ntok * m.al_emb);
+  m.al_pns_w = m.P.add(s + "project_to_n_symbols.weight", (long long)m.al_ntok * D);
+  m.al_pns_b = m.P.add(s + "project_to_n_symbols.bias", m.al_ntok);
+  m.al_query = m.P.add(a + "query_layer.linear_layer.weight", (long long)D * D);
+  m.al_memory = m.P.add(a + "memory_layer.linear_layer.weight", (long long)D * D);
+  m.al_v = m.P.add(a + "v.linear_layer.weight", D);
+  m.al_loc = m.P.add(a + "location_layer.location_conv.conv.weight", (long long)kAlLocF * 2 * kAlLocK);
+  m.al_dense = m.P.add(a + "location_layer.location_dense.linear_layer.weight", (long long)D * kAlLocF);
+  m.al_wih = m.P.add(s + "decoder_rnn.weight_ih", 4LL * D * (D + m.al_emb));
+  m.al_whh = m.P.add(s + "decoder_rnn.weight_hh", 4LL * D * D);
+  m.al_bih = m.P.add(s + "decoder_rnn.bias_ih", 4 * D);
+  m.al_bhh = m.P.add(s + "decoder_rnn.bias_hh", 4 * D);
+  m.al_ph_w = m.P.add(s + "project_to_hidden.0.linear_layer.weight", (long long)D * 2 * D);
+  m.al_ph_b = m.P.add(s + "project_to_hidden.0.linear_layer.bias", D);
+  return ST_OK;
+}
+
 // MultiPeriodDiscriminator: DiscriminatorP(p) for each period (discriminators.py:132-141); each is
 // 5 weight-norm Conv2d (k, 1) stride (3, 1) [the last stride 1] + conv_post (3, 1)
 // (discriminators.py:96-106), i.e. 1-d convs along T/p with the same weight memory layout
@@ -699,6 +766,14 @@ void finalize_layout(Model& m) {
   for (auto* bn : m.bns) {
     bn->off = a;
     a += rup((size_t)2 * bn->C * 4, ALIGN);
+  }
+  if (m.kind == STTS_KIND_ALIGNER) {
+    m.al_wc_t = a;  // [context (128); h (128)][512 gate rows]
+    a += rup((size_t)2 * kAlDec * 4 * kAlDec * 4, ALIGN);
+    m.al_wq_t = a;  // [h (128)][128]
+    a += rup((size_t)kAlDec * kAlDec * 4, ALIGN);
+    m.al_wloc_t = a;  // [channel (2) x tap (63)][32 filters]
+    a += rup((size_t)2 * kAlLocK * kAlLocF * 4, ALIGN);
   }
   m.aux_bytes = a;
   size_t sc = 0;
@@ -1720,6 +1795,93 @@ int pitch_forward(Ctx& c, const float* mel, int T, float* f0, float* gan, float*
   return 0;
 }
 
+// --------------------------------------------------------------------- text aligner forward
+// ASRCNN.forward (Modules/ASR/models.py:37-48), eval mode.  The CNN sees the zero-padded batch as it is (GroupNorm
+// statistics over all L frames); only the attention reads pad_mask.  Everything the recurrence does not feed back is
+// a product outside it: the embedded tokens through W_ih[:, :E] (+ both biases), memory_layer(memory), and after the
+// loop project_to_hidden and project_to_n_symbols over the stored [h; context] rows.
+struct AlignIO {
+  const float* mel;
+  const unsigned char *pad_mask, *unk_mask;
+  const int* tokens;
+  int T, Tt;  // Tt = 0: no tokens, the CNN outputs alone
+  float *ctc, *s2s, *attn, *feature;
+};
+int aligner_forward(Ctx& c, const AlignIO& io) {
+  Model& m = *c.m;
+  if (c.dtype != ST_FP32) return ST_EDTYPE;  // fp32 storage: STTS_FP32 and STTS_SPLIT (the dtype is the convs')
+  const int B = c.B, T = io.T, L = (T + 1) / 2, H = kAlHid, D = kAlDec, E = m.al_emb, steps = io.Tt + 1;
+  if (L > ST_ALIGNER_MAX_L) return ST_EINVAL;
+  const long long rows = (long long)B * L, srows = (long long)B * steps;
+  auto f32 = [&](long long n) { return reinterpret_cast<float*>(c.alloc((size_t)n * 4)); };
+  const Buf M = c.frames(T, 64), X = c.frames(L, H), Y = c.frames(L, H), R = c.frames(L, H), F = c.frames(L, D);
+  float* C1 = f32(rows * H);
+  float *EMB = nullptr, *GIN = nullptr, *PM = nullptr, *HC = nullptr, *HID = nullptr;
+  if (io.Tt > 0) {
+    EMB = f32(srows * E);
+    GIN = f32(srows * 4 * D);
+    PM = f32(rows * D);
+    HC = f32(srows * 2 * D);
+    HID = f32(srows * D);
+  }
+  c.stats_begin = c.stats_off = c.off;  // (no statistics region: nothing of the workspace needs clearing)
+  float* x = reinterpret_cast<float*>(X.p);
+  RUN(st_mfcc_frames(io.mel, c.P(m.al_dct), B, kAlMel, T, kAlMfcc, M.ld, reinterpret_cast<float*>(M.p), c.s));
+  {
+    ConvParams p = conv_base(c, m.al_init, M, 0);
+    p.stride = 2;
+    p.pad = 3;
+    p.Lq = L;
+    conv_out(p, c, X, 0, L);
+    RUN(conv_run(c, p));
+  }
+  for (const auto& l : m.al_layers) {
+    for (const auto& b : l.blk) {
+      ConvParams p = conv_base(c, b.c1, X, 0);
+      p.dil = p.pad = b.dil;
+      p.Lq = L;
+      conv_out(p, c, Y, 0, L);
+      RUN(conv_run(c, p));
+      float* y = reinterpret_cast<float*>(Y.p);
+      RUN(st_groupnorm(y, B, L, H, H, 8, 1, c.P(b.gn_w), c.P(b.gn_b), 1e-5f, y, c.s));  // ReLU -> GroupNorm(8)
+      ConvParams q = conv_base(c, b.c2, Y, 0);
+      q.pad = 1;
+      q.Lq = L;
+      conv_out(q, c, R, 0, L);
+      q.epi_lrelu = 1;  // ReLU, then + the block's input (the engines' epilogue adds a residual before activating)
+      q.epi_slope = 0.f;
+      RUN(conv_run(c, q));
+      RUN(st_add(x, reinterpret_cast<const float*>(R.p), rows * H, c.s));
+    }
+    RUN(st_groupnorm(x, B, L, H, H, 1, 0, c.P(l.gn_w), c.P(l.gn_b), 1e-5f, x, c.s));
+  }
+  {
+    ConvParams p = conv_base(c, m.al_proj, X, 0);
+    p.Lq = L;
+    conv_out(p, c, F, 0, L);
+    RUN(conv_run(c, p));
+  }
+  const float* mem = reinterpret_cast<const float*>(F.p);  // [B][L][128]: x.transpose(1, 2), the attention's memory
+  if (io.feature) RUN(st_frames_to_ncl(mem, B, L, D, io.feature, c.s));
+  if (io.ctc) {
+    RUN(st_gemm_nt(mem, rows, D, D, c.P(m.al_ctc_w[0]), H, D, c.P(m.al_ctc_b[0]), nullptr, 1, C1, H, c.s));
+    RUN(st_gemm_nt(C1, rows, H, H, c.P(m.al_ctc_w[1]), m.al_ntok, H, c.P(m.al_ctc_b[1]), nullptr, 0, io.ctc, m.al_ntok,
+                   c.s));
+  }
+  if (io.Tt <= 0) return 0;
+  RUN(st_s2s_embed(io.tokens, io.unk_mask, B, io.Tt, E, m.al_ntok, c.P(m.al_embw), EMB, c.s));
+  RUN(st_gemm_nt(EMB, srows, E, E, c.P(m.al_wih), 4 * D, E + D, c.P(m.al_bih), c.P(m.al_bhh), 0, GIN, 4 * D, c.s));
+  RUN(st_gemm_nt(mem, rows, D, D, c.P(m.al_memory), D, D, nullptr, nullptr, 0, PM, D, c.s));
+  RUN(st_s2s_decode(GIN, c.aux_f(m.al_wc_t), c.aux_f(m.al_wq_t), c.aux_f(m.al_wloc_t), c.P(m.al_dense), c.P(m.al_v), mem,
+                    PM, io.pad_mask, B, L, steps, io.attn, HC, c.s));
+  if (io.s2s) {
+    RUN(st_gemm_nt(HC, srows, 2 * D, 2 * D, c.P(m.al_ph_w), D, 2 * D, c.P(m.al_ph_b), nullptr, 2, HID, D, c.s));
+    RUN(st_gemm_nt(HID, srows, D, D, c.P(m.al_pns_w), m.al_ntok, D, c.P(m.al_pns_b), nullptr, 0, io.s2s, m.al_ntok,
+                   c.s));
+  }
+  return 0;
+}
+
 // --------------------------------------------------------------------- packing
 int pack_model(Model& m, int dt, char* base, hipStream_t s) {
   char* aux = base + m.aux_off[dt];
@@ -1770,6 +1932,16 @@ int pack_model(Model& m, int dt, char* base, hipStream_t s) {
                         reinterpret_cast<float*>(aux + sm->off), s));
   for (auto* p : m.pools)
     ST_CHECK(st_wn_fold(m.P[p->pool_v], m.P[p->pool_g], p->cin, 3, reinterpret_cast<float*>(aux + p->pool_off), s));
+  if (m.kind == STTS_KIND_ALIGNER) {
+    // the recurrence reads its weights k-major: lanes (output rows) side by side
+    const int D = kAlDec, E = m.al_emb;
+    float* wc = reinterpret_cast<float*>(aux + m.al_wc_t);
+    ST_CHECK(st_transpose(m.P[m.al_wih], 4 * D, D, E + D, E, wc, s));              // W_ih[:, E:] (the context part)
+    ST_CHECK(st_transpose(m.P[m.al_whh], 4 * D, D, D, 0, wc + (size_t)D * 4 * D, s));
+    ST_CHECK(st_transpose(m.P[m.al_query], D, D, D, 0, reinterpret_cast<float*>(aux + m.al_wq_t), s));
+    ST_CHECK(st_transpose(m.P[m.al_loc], kAlLocF, 2 * kAlLocK, 2 * kAlLocK, 0,
+                          reinterpret_cast<float*>(aux + m.al_wloc_t), s));
+  }
   return 0;
 }
 
@@ -1831,6 +2003,12 @@ const Kind kKinds[] = {
     {STTS_KIND_MSD, build_msd, [](Ctx& c, int T) { return msd_forward(c, nullptr, T, nullptr); }},
     {STTS_KIND_PITCH, build_pitch,
      [](Ctx& c, int T) { return pitch_forward(c, nullptr, T, nullptr, nullptr, nullptr, nullptr); }},
+    // (the CNN outputs alone; stts_aligner_workspace_bytes sizes a forward with tokens)
+    {STTS_KIND_ALIGNER, build_aligner, [](Ctx& c, int T) {
+       AlignIO io{};
+       io.T = T;
+       return aligner_forward(c, io);
+     }},
 };
 const Kind* find_kind(int kind) {
   for (const Kind& k : kKinds)
@@ -1973,6 +2151,40 @@ long long stts_pitch_error_offset(const stts_model* mc, int dtype, int B, int T)
 
 int stts_log_norm(const float* mel, int B, int n_mels, int T, float mean, float std, float* out, void* stream) {
   return st_log_norm(mel, B, n_mels, T, mean, std, out, (hipStream_t)stream);
+}
+
+int stts_aligner_fwd(stts_model* m, int dtype, const float* mel, const unsigned char* pad_mask, const int* tokens,
+                     const unsigned char* unk_mask, int B, int T, int Tt, float* ctc, float* s2s_logit, float* attn,
+                     float* feature, void* ws, long long ws_bytes, void* stream) {
+  if (!m || m->kind != STTS_KIND_ALIGNER) return ST_EINVAL;
+  if (dtype == ST_BF16) return ST_EDTYPE;  // the recurrence and GroupNorm are fp32: fp32 storage only
+  if (B <= 0 || T <= 0 || !mel || (tokens && Tt <= 0) || Tt < 0) return ST_EINVAL;
+  ST_CHECK(check_params(*m));
+  AlignIO io{mel, pad_mask, unk_mask, tokens, T, tokens ? Tt : 0, ctc, s2s_logit, attn, feature};
+  if (!tokens) io.s2s = io.attn = nullptr;
+  return with_ctx(m, dtype, B, ws, ws_bytes, stream, [&](Ctx& c) { return aligner_forward(c, io); }, nullptr);
+}
+
+long long stts_aligner_workspace_bytes(const stts_model* mc, int dtype, int B, int T, int Tt) {
+  if (!mc || mc->kind != STTS_KIND_ALIGNER || B <= 0 || T <= 0 || Tt < 0) return ST_EINVAL;
+  if (dtype == ST_BF16) return ST_EDTYPE;
+  AlignIO io{};
+  io.T = T;
+  io.Tt = Tt;
+  size_t need = 0;
+  const int r = with_ctx(const_cast<Model*>(mc), dtype, B, nullptr, 0, nullptr,
+                         [&](Ctx& c) { return aligner_forward(c, io); }, &need);
+  return r ? r : (long long)need;
+}
+
+long long stts_maximum_path_workspace_bytes(int B, int Tx, int Ty) { return st_max_path_workspace_bytes(B, Tx, Ty); }
+
+int stts_maximum_path(const float* value, const int* tx_len, const int* ty_len, int B, int Tx, int Ty, float* path,
+                      void* workspace, long long ws_bytes, void* stream) {
+  if (!value || !tx_len || !ty_len || !path || B <= 0 || Tx <= 0 || Ty <= 0) return ST_EINVAL;
+  for (int b = 0; b < B; ++b)  // the search is undefined outside 1 <= tx <= ty (host values: refused here)
+    if (tx_len[b] < 1 || tx_len[b] > ty_len[b] || tx_len[b] > Tx || ty_len[b] > Ty) return ST_EINVAL;
+  return st_max_path(value, tx_len, ty_len, B, Tx, Ty, path, workspace, ws_bytes, (hipStream_t)stream);
 }
 
 long long stts_mpd_out_elems(const stts_model* m, int B, int T) {

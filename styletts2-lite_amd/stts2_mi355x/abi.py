@@ -32,6 +32,11 @@ SIGNATURES = {
     "stts_pitch_fwd": ([vp, i, vp, i, i, vp, vp, vp, vp, ll, vp], i),
     "stts_pitch_error_offset": ([vp, i, i, i], ll),
     "stts_log_norm": ([vp, i, i, i, f, f, vp, vp], i),
+    # text aligner, monotonic alignment search (the search's lengths are host arrays)
+    "stts_aligner_fwd": ([vp, i, vp, vp, vp, vp, i, i, i, vp, vp, vp, vp, vp, ll, vp], i),
+    "stts_aligner_workspace_bytes": ([vp, i, i, i, i], ll),
+    "stts_maximum_path_workspace_bytes": ([i, i, i], ll),
+    "stts_maximum_path": ([vp, pi, pi, i, i, i, vp, vp, ll, vp], i),
     # MultiPeriodDiscriminator
     "stts_mpd_out_elems": ([vp, i, i], ll),
     "stts_mpd_fwd": ([vp, i, vp, i, i, vp, ll, vp, ll, vp], i),

@@ -1,0 +1,170 @@
+"""Drop-in for Modules/ASR/models.py: ASRCNN, the text aligner of the training step.
+
+train.py opens every iteration with `ppgs, s2s_pred, s2s_attn = model.text_aligner(mels, mask, texts)` (:206, and
+:381 in validation).  This module holds the reference's 143 state-dict entries (so `load_state_dict(strict=True)`
+takes a checkpoint's `text_aligner` block) and runs the eval-mode forward under no_grad on the HIP plan
+(engine.AlignerEngine -> stts_aligner_fwd): the conv stack on the conv engines, the S2S attention decoder's
+Tt + 1 steps as one persistent launch.  Training the aligner (its backward, loss_s2s / loss_mono, its optimizer
+step, train-mode dropout) is not built: train mode raises.
+
+`to_mfcc.dct_mat` is torchaudio's create_dct(40, 80, 'ortho'), computed here from its formula (torchaudio is not a
+dependency); after load_state_dict the checkpoint's own buffer runs.
+"""
+from __future__ import annotations
+
+import math
+
+import torch
+from torch import nn
+
+
+def create_dct(n_mfcc: int, n_mels: int) -> torch.Tensor:
+    """torchaudio.functional.create_dct(n_mfcc, n_mels, 'ortho'): [n_mels, n_mfcc] fp32."""
+    n = torch.arange(float(n_mels))
+    k = torch.arange(float(n_mfcc)).unsqueeze(1)
+    dct = torch.cos(math.pi / float(n_mels) * (n + 0.5) * k)  # [n_mfcc, n_mels]
+    dct[0] *= 1.0 / math.sqrt(2.0)
+    dct *= math.sqrt(2.0 / float(n_mels))
+    return dct.t().contiguous()
+
+
+class MFCC(nn.Module):
+    def __init__(self, n_mfcc=40, n_mels=80):
+        super().__init__()
+        self.n_mfcc, self.n_mels, self.norm = n_mfcc, n_mels, "ortho"
+        self.register_buffer("dct_mat", create_dct(n_mfcc, n_mels))
+
+
+class LinearNorm(nn.Module):
+    def __init__(self, in_dim, out_dim, bias=True, w_init_gain="linear"):
+        super().__init__()
+        self.linear_layer = nn.Linear(in_dim, out_dim, bias=bias)
+        nn.init.xavier_uniform_(self.linear_layer.weight, gain=nn.init.calculate_gain(w_init_gain))
+
+
+class ConvNorm(nn.Module):
+    def __init__(self, in_channels, out_channels, kernel_size=1, stride=1, padding=None, dilation=1, bias=True):
+        super().__init__()
+        if padding is None:
+            padding = dilation * (kernel_size - 1) // 2
+        self.conv = nn.Conv1d(in_channels, out_channels, kernel_size=kernel_size, stride=stride, padding=padding,
+                              dilation=dilation, bias=bias)
+        nn.init.xavier_uniform_(self.conv.weight, gain=nn.init.calculate_gain("linear"))
+
+
+class ConvBlock(nn.Module):
+    """reference Modules/ASR/layers.py:105-131 (parameter layout)."""
+
+    def __init__(self, hidden_dim, n_conv=3, dropout_p=0.2):
+        super().__init__()
+        self.blocks = nn.ModuleList([nn.Sequential(
+            ConvNorm(hidden_dim, hidden_dim, kernel_size=3, padding=3 ** i, dilation=3 ** i),
+            nn.ReLU(),
+            nn.GroupNorm(num_groups=8, num_channels=hidden_dim),
+            nn.Dropout(p=dropout_p),
+            ConvNorm(hidden_dim, hidden_dim, kernel_size=3, padding=1, dilation=1),
+            nn.ReLU(),
+            nn.Dropout(p=dropout_p)) for i in range(n_conv)])
+
+
+class LocationLayer(nn.Module):
+    def __init__(self, n_filters, kernel_size, attention_dim):
+        super().__init__()
+        self.location_conv = ConvNorm(2, n_filters, kernel_size=kernel_size, padding=(kernel_size - 1) // 2,
+                                      bias=False)
+        self.location_dense = LinearNorm(n_filters, attention_dim, bias=False, w_init_gain="tanh")
+
+
+class Attention(nn.Module):
+    def __init__(self, rnn_dim, embedding_dim, attention_dim, n_filters, kernel_size):
+        super().__init__()
+        self.query_layer = LinearNorm(rnn_dim, attention_dim, bias=False, w_init_gain="tanh")
+        self.memory_layer = LinearNorm(embedding_dim, attention_dim, bias=False, w_init_gain="tanh")
+        self.v = LinearNorm(attention_dim, 1, bias=False)
+        self.location_layer = LocationLayer(n_filters, kernel_size, attention_dim)
+
+
+class ASRS2S(nn.Module):
+    """reference Modules/ASR/models.py:74-100 (parameter layout)."""
+
+    def __init__(self, embedding_dim=256, hidden_dim=512, n_location_filters=32, location_kernel_size=63, n_token=40):
+        super().__init__()
+        self.embedding = nn.Embedding(n_token, embedding_dim)
+        val_range = math.sqrt(6 / hidden_dim)
+        self.embedding.weight.data.uniform_(-val_range, val_range)
+        self.decoder_rnn_dim = hidden_dim
+        self.project_to_n_symbols = nn.Linear(hidden_dim, n_token)
+        self.attention_layer = Attention(hidden_dim, hidden_dim, hidden_dim, n_location_filters, location_kernel_size)
+        self.decoder_rnn = nn.LSTMCell(hidden_dim + embedding_dim, hidden_dim)
+        self.project_to_hidden = nn.Sequential(LinearNorm(hidden_dim * 2, hidden_dim), nn.Tanh())
+        self.sos, self.eos, self.unk_index, self.random_mask = 1, 2, 3, 0.1
+
+
+class ASRCNN(nn.Module):
+    """reference Modules/ASR/models.py:8-72."""
+
+    def __init__(self, input_dim=80, hidden_dim=256, n_token=35, n_layers=6, token_embedding_dim=256):
+        super().__init__()
+        self.n_token = n_token
+        self.n_down = 1
+        self.cfg = [input_dim, hidden_dim, n_token, n_layers, token_embedding_dim]
+        self.to_mfcc = MFCC()
+        self.init_cnn = ConvNorm(input_dim // 2, hidden_dim, kernel_size=7, padding=3, stride=2)
+        self.cnns = nn.Sequential(*[nn.Sequential(ConvBlock(hidden_dim), nn.GroupNorm(num_groups=1,
+                                                                                      num_channels=hidden_dim))
+                                    for _ in range(n_layers)])
+        self.projection = ConvNorm(hidden_dim, hidden_dim // 2)
+        self.ctc_linear = nn.Sequential(LinearNorm(hidden_dim // 2, hidden_dim), nn.ReLU(),
+                                        LinearNorm(hidden_dim, n_token))
+        self.asr_s2s = ASRS2S(embedding_dim=token_embedding_dim, hidden_dim=hidden_dim // 2, n_token=n_token)
+        self._engine = None
+
+    def invalidate(self):
+        """Drop the packed weights (after writes through `param.data`, which stale() cannot see)."""
+        self._engine = None
+
+    def engine(self, dtype="fp32"):
+        from .engine import AlignerEngine
+        if self._engine is None or self._engine.dtype != dtype or self._engine.stale(self):
+            self._engine = AlignerEngine(self, dtype=dtype)
+        return self._engine
+
+    def _check(self):
+        if self.training:
+            raise NotImplementedError("ASRCNN: the HIP path is the eval-mode forward under no_grad (no dropout, no "
+                                      "backward: training the aligner is not built); call .eval() first")
+        if self.cfg[0] != 80 or self.cfg[1] != 256:
+            raise NotImplementedError("ASRCNN: the HIP plan is built for input_dim = 80, hidden_dim = 256 (the "
+                                      "reference's)")
+
+    def draw_unk_mask(self, text_input):
+        """models.py:126: the 10 % unknown-token draw, on the host as the reference's, so torch.manual_seed
+        reproduces it."""
+        return torch.rand(text_input.shape) < self.asr_s2s.random_mask
+
+    def forward(self, x, src_key_padding_mask=None, text_input=None, dtype="fp32", unk_mask=None):
+        """mel [B, 80, T] -> ctc_logit [B, L, n_token], or with text_input [B, Tt] (ctc_logit, s2s_logit
+        [B, Tt + 1, n_token], s2s_attn [B, Tt + 1, L]); L = ceil(T / 2).  unk_mask (bool [B, Tt]): the tokens
+        replaced by the unknown index, drawn as the reference does when None."""
+        self._check()
+        if text_input is None:
+            with torch.no_grad():
+                return self.engine(dtype).forward(x, s2s=False, attn=False)[0]
+        tok = text_input.detach().cpu()
+        if tok.numel() and (int(tok.min()) < 0 or int(tok.max()) >= self.n_token):
+            raise IndexError(f"ASRCNN: token indices must lie in [0, {self.n_token})")
+        if unk_mask is None:
+            unk_mask = self.draw_unk_mask(text_input)
+        with torch.no_grad():
+            ctc, s2s, attn, _ = self.engine(dtype).forward(x, src_key_padding_mask, text_input, unk_mask)
+        return ctc, s2s, attn
+
+    def get_feature(self, x, dtype="fp32"):
+        """The projection output [B, 128, L] (models.py:50-55)."""
+        self._check()
+        with torch.no_grad():
+            return self.engine(dtype).forward(x.squeeze(1) if x.dim() == 4 else x, ctc=False, feature=True)[3]
+
+    def length_to_mask(self, lengths):
+        mask = torch.arange(lengths.max()).unsqueeze(0).expand(lengths.shape[0], -1).type_as(lengths)
+        return torch.gt(mask + 1, lengths.unsqueeze(1)).to(lengths.device)

@@ -18,6 +18,7 @@ from .abi import SIGNATURES
 
 KIND_HIFIGAN, KIND_ISTFTNET, KIND_F0N, KIND_STYLE, KIND_MPD, KIND_VOCOS, KIND_MSD = 0, 1, 2, 3, 4, 5, 6
 KIND_PITCH = 8  # (7 is not a kind: include/stts2.h)
+KIND_ALIGNER = 9
 DTYPES = {"fp32": 0, "bf16": 1, "bf16x3": 2}  # bf16x3: the split-operand accuracy mode (STTS_SPLIT)
 
 _LIB = None
@@ -443,6 +444,58 @@ class PitchEngine(_Engine):
         if in_dev.type != "cuda":
             f0, gan, pool = (t.to(in_dev) if t is not None else None for t in (f0, gan, pool))
         return f0, gan, pool
+
+
+class AlignerEngine(_Engine):
+    """HIP forward of Modules/ASR/models.py ASRCNN (reference :37-48, eval mode): the conv stack on the conv engines,
+    the S2S decoder's recurrence as one persistent launch."""
+
+    def __init__(self, module, dtype="fp32"):
+        super().__init__(module, dtype)
+        if dtype == "bf16":
+            raise ValueError("ASRCNN: dtype must be fp32 or bf16x3 (GroupNorm and the recurrence are fp32)")
+        self.n_token = module.n_token
+        self.model = NativeModel(KIND_ALIGNER, module.cfg, module)
+        self.model.pack(dtype)
+
+    def forward(self, mel, pad_mask=None, tokens=None, unk_mask=None, ctc=True, s2s=True, attn=True, feature=False):
+        """mel [B, 80, T] -> (ctc [B, L, n_token], s2s_logit [B, Tt + 1, n_token], attn [B, Tt + 1, L], feature
+        [B, 128, L]); an output that is switched off, or that needs tokens when there are none, is None (a null
+        pointer to the library)."""
+        dev = self.model.device
+        mel = _dev_f32(mel, dev)
+        if mel.dim() != 3 or mel.shape[1] != 80 or mel.shape[0] < 1 or mel.shape[2] < 1:
+            raise ValueError(f"mel must be [B, 80, T], got {tuple(mel.shape)}")
+        B, _, T = mel.shape
+        L = (T + 1) // 2
+        as_bytes = lambda t: t.to(device=dev).ne(0).to(torch.uint8).contiguous()  # noqa: E731
+        if pad_mask is not None:
+            if tuple(pad_mask.shape) != (B, L):
+                raise ValueError(f"src_key_padding_mask must be [B, {L}], got {tuple(pad_mask.shape)}")
+            pad_mask = as_bytes(pad_mask)
+        Tt = 0
+        if tokens is not None:
+            if tokens.dim() != 2 or tokens.shape[0] != B or tokens.shape[1] < 1:
+                raise ValueError(f"text_input must be [B, T_text >= 1], got {tuple(tokens.shape)}")
+            Tt = tokens.shape[1]
+            tokens = tokens.to(device=dev, dtype=torch.int32).contiguous()
+            if unk_mask is not None:
+                if tuple(unk_mask.shape) != (B, Tt):
+                    raise ValueError(f"unk_mask must be [B, {Tt}], got {tuple(unk_mask.shape)}")
+                unk_mask = as_bytes(unk_mask)
+        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
+        o_ctc = new(B, L, self.n_token) if ctc else None
+        o_s2s = new(B, Tt + 1, self.n_token) if s2s and Tt else None
+        o_attn = new(B, Tt + 1, L) if attn and Tt else None
+        o_feat = new(B, 128, L) if feature else None
+        dt = DTYPES[self.dtype]
+        nb = query("stts_aligner_workspace_bytes", self.model.h, dt, B, T, Tt)
+        ws = self.model._ws.get(self.dtype)
+        if ws is None or ws.numel() < nb:
+            self.model._ws[self.dtype] = ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
+        call("stts_aligner_fwd", self.model.h, dt, mel, pad_mask, tokens, unk_mask if Tt else None, B, T, Tt, o_ctc,
+             o_s2s, o_attn, o_feat, ws, nb)
+        return o_ctc, o_s2s, o_attn, o_feat
 
 
 def log_norm(x, mean=-4, std=4, dim=2):

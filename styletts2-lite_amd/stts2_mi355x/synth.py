@@ -139,6 +139,8 @@ def is_fixed_buffer(key: str) -> bool:
     """Deterministic buffers the modules compute themselves (CustomSTFT bases)."""
     if key.endswith("num_batches_tracked"):  # BatchNorm's step counter: the module's own value stays
         return True
+    if key.endswith("to_mfcc.dct_mat"):  # the text aligner's DCT basis (asr.create_dct)
+        return True
     return ".stft." in key and not key.endswith((".out.weight", ".out.bias"))  # Vocos ISTFTHead.out is a Linear
 
 

@@ -23,7 +23,10 @@ and lambda_norm smooth_l1(N_real, N_fake) to g_loss (:269-270, 300-307) and step
 style encoder after the decoder's backward (:323-324).  F0_real and N_real are the caller's tensors, or, with
 `pitch_extractor=` (a jdc.JDCNet in eval mode) and none given, what train.py:260-262 computes from gt under no_grad:
 F0_real = pitch_extractor(gt.unsqueeze(1))[0] and N_real = log_norm(gt.unsqueeze(1)).squeeze(1), both on the HIP path
-(`TrainStep.targets(gt)`); the extractor is frozen: no optimizer, no gradient.  With `text_encoder=` (and the predictor) the step starts where train.py's G step starts
+(`TrainStep.targets(gt)`); the extractor is frozen: no optimizer, no gradient.  With `text_aligner=` (an asr.ASRCNN in
+eval mode, frozen in the same way) a `text=` dict may leave out attn / attn_mono and give `mel_input_length` (and
+optionally `unk_mask`, `mono`): `TrainStep.align` then computes both as train.py:203-214 does (the aligner on the HIP
+path, mask_from_lens, maximum_path), and asr uses the monotonic one unless mono=False.  With `text_encoder=` (and the predictor) the step starts where train.py's G step starts
 (train.py:217-262), from the tokens:
 
     losses = step(None, None, None, None, wav, gt=None, F0_real=F0_real, N_real=N_real,
@@ -70,9 +73,10 @@ class TrainStep:
     def __init__(self, decoder, mpd, msd, lr_dec=1e-5, lr_disc=1e-4, lambda_mel=5.0, lambda_gen=1.0, dtype="fp32",
                  freeze_d_in_g=True, capture=False, predictor=None, style_encoder=None, lr_pred=1e-4, lr_style=1e-5,
                  lambda_F0=1.0, lambda_norm=1.0, text_encoder=None, lr_text=1e-4, lambda_dur=1.0, lambda_ce=1.0,
-                 graph=False, pitch_extractor=None):
+                 graph=False, pitch_extractor=None, text_aligner=None):
         self.decoder, self.mpd, self.msd = decoder, mpd, msd
         self.pitch_extractor = pitch_extractor  # frozen (train.py:260-261): no optimizer, no gradient
+        self.text_aligner = text_aligner  # frozen too (an asr.ASRCNN in eval mode; freeze_modules: text_aligner)
         self.predictor, self.style_encoder, self.text_encoder = predictor, style_encoder, text_encoder
         self.lambda_dur, self.lambda_ce = float(lambda_dur), float(lambda_ce)
         self.lambda_F0, self.lambda_norm = float(lambda_F0), float(lambda_norm)
@@ -189,6 +193,23 @@ class TrainStep:
             N_real = log_norm(gt.unsqueeze(1)).squeeze(1)
         return F0_real, N_real
 
+    def align(self, mels, mel_input_length, texts, input_lengths, unk_mask=None):
+        """train.py:203-214 under no_grad: (s2s_attn [B, T_text, L], s2s_attn_mono) of the padded batch mels
+        [B, 80, T_mel]: the aligner with the padding mask of mel_input_length // 2, the SOS step dropped,
+        mask_from_lens, maximum_path.  unk_mask: the aligner's unknown-token mask (drawn as the reference does
+        when None)."""
+        from .align import mask_from_lens, maximum_path
+        if self.text_aligner is None:
+            raise ValueError("TrainStep.align needs text_aligner=")
+        with torch.no_grad():
+            L = (mels.shape[-1] + 1) // 2
+            half = torch.as_tensor(mel_input_length).to(mels.device) // (2 ** self.text_aligner.n_down)
+            mask = torch.arange(L, device=mels.device)[None, :] + 1 > half[:, None]  # length_to_mask (:203)
+            _, _, s2s_attn = self.text_aligner(mels, mask, texts, unk_mask=unk_mask)
+            s2s_attn = s2s_attn[:, 1:, :].contiguous()  # :207-209
+            mask_ST = mask_from_lens(s2s_attn, torch.as_tensor(input_lengths), half)
+            return s2s_attn, maximum_path(s2s_attn, mask_ST)
+
     def _text_front(self, text):
         """train.py:217-251: the text encoder, asr, the predictor's forward and the crops."""
         from .prosody import matmul
@@ -196,7 +217,15 @@ class TrainStep:
         if self.text_encoder is None or self.predictor is None:
             raise ValueError("TrainStep(text=...) needs text_encoder= and predictor=")
         texts, lens = text["texts"], text["input_lengths"]
-        attn, mono = text["attn"], text["attn_mono"]
+        if "attn" in text or "attn_mono" in text:
+            attn, mono = text["attn"], text["attn_mono"]
+        else:  # train.py:203-214 from the aligner; `mono` stands in for the coin of :220
+            if self.text_aligner is None or "mel_input_length" not in text:
+                raise ValueError("TrainStep(text=...) without attn / attn_mono needs text_aligner= and "
+                                 "text['mel_input_length']")
+            attn, mono = self.align(text["mels"], text["mel_input_length"], texts, lens, text.get("unk_mask"))
+            if text.get("mono", True):
+                attn = mono
         t_en = self.text_encoder(texts, lens)  # train.py:217
         asr = matmul(t_en, attn)  # :220-223
         d_gt = mono.sum(axis=-1).detach()  # :225
