@@ -323,6 +323,67 @@ int stts_cistft_head_fwd(const float* post, const float* br, const float* bi, in
 int stts_cistft_head_bwd(const float* post, const float* br, const float* bi, const float* dy, int B, int F, int n_fft,
                          int hop, float* dpost, void* stream);
 
+/* ---- The text aligner's S2S decoder under train.py's step (Modules/ASR/models.py ASRS2S :118-176; train.py:206,
+ * 301-306; csrc/aligner_train.hip).  The decoder is built for hidden_dim = 128 (decoder, attention and memory width),
+ * 32 location filters of 63 taps.  `params` / `grads` are HOST arrays of 14 DEVICE pointers in ASRS2S's
+ * named_parameters() order:
+ *    0 embedding.weight [n_token][E]                      7 ...location_dense.linear_layer.weight [128][32]
+ *    1 project_to_n_symbols.weight [n_token][128]         8 decoder_rnn.weight_ih [512][E + 128]
+ *    2 project_to_n_symbols.bias [n_token]                9 decoder_rnn.weight_hh [512][128]
+ *    3 attention_layer.query_layer...weight [128][128]   10 decoder_rnn.bias_ih [512]
+ *    4 attention_layer.memory_layer...weight [128][128]  11 decoder_rnn.bias_hh [512]
+ *    5 attention_layer.v...weight [1][128]               12 project_to_hidden.0.linear_layer.weight [128][256]
+ *    6 ...location_conv.conv.weight [32][2][63]          13 project_to_hidden.0.linear_layer.bias [128]
+ * Frame caps: L <= 4096 for the forward (STTS_ALIGNER_MAX_L) and L <= STTS_S2S_BWD_MAX_L for the backward, whose
+ * workgroup keeps five [L] arrays (83 KB at the cap) next to 61 KB of tiles and state in the 160 KiB of a CU; above
+ * the cap STTS_EINVAL, checked on the host (the workspace queries return it as a negative size).  1 <= E <= 1024,
+ * 4 <= n_token <= 65536, Tt >= 1. */
+#define STTS_S2S_BWD_MAX_L 4096
+
+/* ASRS2S.forward (models.py:118-147) for training:
+ *   memory       [B][L][128]    the CNN feature, frames (models.py:124)
+ *   memory_mask  bytes [B][L], 1 = padded frame (the attention's masked_fill, layers.py), or NULL
+ *   tokens       int32 [B][Tt]  text_input (:127); indices in [0, n_token): the caller checks
+ *   unk_mask     bytes [B][Tt]  the random_mask draw of :126 (1 = replaced by index 3), or NULL
+ *   drop_scale   [B][Tt + 1][128]  keep mask / (1 - p) of F.dropout(hidden, 0.5) (:174), or NULL (eval: no dropout)
+ *   hidden       [B][Tt + 1][128], logit [B][Tt + 1][n_token], attn [B][Tt + 1][L]   the three outputs (:143-147)
+ *   save         stts_s2s_save_bytes(B, L, Tt) bytes kept for stts_s2s_bwd: per step the four gate activations, the
+ *                cell state, the cumulative weights before the step, [h; context], and the processed memory.  NULL:
+ *                nothing is kept (the forward without grad), and the plain decoder kernel of stts_aligner_fwd runs.
+ * Workspace >= stts_s2s_fwd_train_workspace_bytes(B, L, Tt, n_token, E). */
+long long stts_s2s_save_bytes(int B, int L, int Tt);
+long long stts_s2s_fwd_train_workspace_bytes(int B, int L, int Tt, int n_token, int E);
+int stts_s2s_fwd_train(const float* memory, const unsigned char* memory_mask, const int* tokens,
+                       const unsigned char* unk_mask, const float* const* params, int B, int L, int Tt, int n_token,
+                       int E, const float* drop_scale, float* hidden, float* logit, float* attn, void* save, void* ws,
+                       long long ws_bytes, void* stream);
+/* Its backward: the same memory, masks, tokens, params and drop_scale; hidden, attn and save from the forward;
+ * dhidden / dlogit / dattn = the upstream gradients of the three outputs (each nullable: zero).  Writes dmemory
+ * [B][L][128] (nullable; exactly 0 at masked frames) and grads[14] (a NULL entry: not computed, the others
+ * unchanged bit for bit).  One persistent workgroup per utterance walks the steps backwards; every weight gradient
+ * is a fixed-order product over all rows after it, the embedding rows (SOS into row 1, unknown-masked tokens into
+ * row 3) are scattered in row order: bitwise reproducible, and a row of dmemory does not depend on the batch.
+ * Workspace >= stts_s2s_bwd_workspace_bytes(B, L, Tt, n_token, E). */
+long long stts_s2s_bwd_workspace_bytes(int B, int L, int Tt, int n_token, int E);
+int stts_s2s_bwd(const float* memory, const unsigned char* memory_mask, const int* tokens,
+                 const unsigned char* unk_mask, const float* const* params, int B, int L, int Tt, int n_token, int E,
+                 const float* drop_scale, const float* hidden, const float* attn, const void* save,
+                 const float* dhidden, const float* dlogit, const float* dattn, float* dmemory, float* const* grads,
+                 void* ws, long long ws_bytes, void* stream);
+
+/* loss_s2s (train.py:301-304) over logits [B][T][K] (rows ls_b / ls_t apart), tokens int64 [B][..] (rows tok_b
+ * apart) and the text lengths (device int32 [B], NULL = T): loss (device, 1 double) = mean_b cross_entropy(logits[b,
+ * :len_b], tokens[b, :len_b]) in fp64, utterance order.  With dlogits [B][T][K] (nullable) also g times its gradient
+ * (rows >= len_b zero), g read from a DEVICE float (NULL: 0).  Workspace >= stts_s2s_loss_workspace_bytes(B). */
+long long stts_s2s_loss_workspace_bytes(int B);
+int stts_s2s_loss(const float* logits, long long ls_b, long long ls_t, int B, int T, int K, const long long* tokens,
+                  long long tok_b, const int* lengths, double* loss, float* dlogits, const float* g, void* ws,
+                  long long ws_bytes, void* stream);
+/* loss_mono (train.py:306) = 10 l1_loss(attn, attn_mono) over n values: loss (device, 1 double; a fixed-order fp64
+ * sum) and, with dattn (nullable), g 10 / n sign(attn - attn_mono) (sign(0) = 0), g a DEVICE float (NULL: 0). */
+int stts_mono_loss(const float* attn, const float* attn_mono, long long n, double* loss, float* dattn, const float* g,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,32 +12,17 @@
 // Everything here is fp32 with every sum in a fixed order and no atomics: a row of a batch is bitwise the B = 1 result.
 #include "common.h"
 #include "kernels.h"
+#include "s2s_common.h"
 
 namespace {
+
+using namespace s2s;
 
 constexpr int NT = 256;
 
 unsigned grid_of(long long n) {
   const long long g = (n + NT - 1) / NT;
   return (unsigned)(g < 65536 ? (g > 0 ? g : 1) : 65536);
-}
-
-// sum / max over the workgroup in a fixed order: a butterfly inside each wave, then the waves' values in wave order.
-// red holds one float per wave; two barriers, so red can be reused right after.
-template <bool MAX>
-__device__ __forceinline__ float block_reduce(float v, float* red) {
-#pragma unroll
-  for (int s = 32; s >= 1; s >>= 1) {
-    const float o = __shfl_xor(v, s);
-    v = MAX ? fmaxf(v, o) : v + o;
-  }
-  const int nw = (int)(blockDim.x >> 6);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float r = red[0];
-  for (int w = 1; w < nw; ++w) r = MAX ? fmaxf(r, red[w]) : r + red[w];
-  __syncthreads();
-  return r;
 }
 
 __global__ void __launch_bounds__(NT) k_mfcc_frames(const float* __restrict__ mel, const float* __restrict__ dct, int B,
@@ -187,20 +172,17 @@ __global__ void __launch_bounds__(NT) k_embed(const int* __restrict__ tok, const
 // [embedding part (hoisted, gin); context; h], the location-sensitive attention over the L memory frames, the context.
 // The state (h, context, previous and cumulative weights) stays in LDS, the cell state in registers; the recurrent
 // weights (k-major) and memory / processed memory stream from L2.  No workgroup waits for another one.
-constexpr int DT = 512;                    // threads
-constexpr int DH = 128;                    // decoder_rnn_dim = attention_dim = memory width
-constexpr int DF = 32, DK = 63, DP = 31;   // location conv: filters, taps, padding
-constexpr int DTL = 128;                   // frames per location-conv tile
-constexpr int DSTRIP = 8;                  // frames per thread of the location conv
-
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
-
+// SAVE (the training forward, stts_s2s_fwd_train): every step also stores what the backward reads, the four gate
+// activations [B][steps][4 DH], the cell state [B][steps][DH] and the cumulative weights before the step [B][steps][L].
+template <bool SAVE>
 __global__ void __launch_bounds__(DT) k_s2s_decode(const float* __restrict__ gin, const float* __restrict__ wc_t,
                                                    const float* __restrict__ wq_t, const float* __restrict__ wloc_t,
                                                    const float* __restrict__ wd, const float* __restrict__ vv,
                                                    const float* __restrict__ mem, const float* __restrict__ pmem,
                                                    const unsigned char* __restrict__ mask, int L, int steps,
-                                                   float* __restrict__ attn, float* __restrict__ hc) {
+                                                   float* __restrict__ attn, float* __restrict__ hc,
+                                                   float* __restrict__ sv_gates, float* __restrict__ sv_cell,
+                                                   float* __restrict__ sv_cum) {
   extern __shared__ float dyn[];
   __shared__ float s_h[DH], s_ctx[DH], s_q[DH], s_gates[4 * DH], s_part[4 * DH], s_red[DT / 64];
   __shared__ float s_wloc[2 * DK * DF], s_conv[DTL * (DF + 1)];
@@ -243,6 +225,14 @@ __global__ void __launch_bounds__(DT) k_s2s_decode(const float* __restrict__ gin
       const float h = og * tanhf(cell);
       s_h[tid] = h;
       hc[((size_t)b * steps + t) * (2 * DH) + tid] = h;
+      if (SAVE) {
+        float* g = sv_gates + ((size_t)b * steps + t) * (4 * DH);
+        g[tid] = ig;
+        g[DH + tid] = fg;
+        g[2 * DH + tid] = gg;
+        g[3 * DH + tid] = og;
+        sv_cell[((size_t)b * steps + t) * DH + tid] = cell;
+      }
     }
     __syncthreads();
     // 2. the query projection: 4 partial sums of 32 k each, added in part order
@@ -258,27 +248,7 @@ __global__ void __launch_bounds__(DT) k_s2s_decode(const float* __restrict__ gin
     __syncthreads();
     // 3-5. per tile of DTL frames: the location conv into LDS, then dense + tanh + v
     for (int l0 = 0; l0 < L; l0 += DTL) {
-      {
-        const int f = tid & (DF - 1), strip = tid >> 5, lb = l0 + strip * DSTRIP;
-        if (lb < L) {
-          float acc[DSTRIP] = {};
-#pragma unroll
-          for (int c = 0; c < 2; ++c) {
-            const float* arr = (c ? s_wc : s_wp) + lb;  // arr[j + k] = frame lb + j + k - DP
-            float win[DSTRIP + DK - 1];
-#pragma unroll
-            for (int j = 0; j < DSTRIP + DK - 1; ++j) win[j] = arr[j];
-#pragma unroll
-            for (int k = 0; k < DK; ++k) {
-              const float w = s_wloc[(c * DK + k) * DF + f];
-#pragma unroll
-              for (int j = 0; j < DSTRIP; ++j) acc[j] = fmaf(w, win[j + k], acc[j]);
-            }
-          }
-#pragma unroll
-          for (int j = 0; j < DSTRIP; ++j) s_conv[(strip * DSTRIP + j) * (DF + 1) + f] = acc[j];
-        }
-      }
+      loc_conv_tile(s_wp, s_wc, s_wloc, l0, L, s_conv);
       __syncthreads();
       const int lend = min(DTL, L - l0);
       for (int li = wave; li < lend; li += DT / 64) {
@@ -318,6 +288,7 @@ __global__ void __launch_bounds__(DT) k_s2s_decode(const float* __restrict__ gin
     // 8. the new weights become the previous ones, cumulative += weights
     for (int l = tid; l < L; l += DT) {
       const float w = s_e[l] / sum;
+      if (SAVE) sv_cum[((size_t)b * steps + t) * L + l] = s_wc[DP + l];
       s_wp[DP + l] = w;
       s_wc[DP + l] += w;
       if (attn) attn[((size_t)b * steps + t) * L + l] = w;
@@ -445,27 +416,46 @@ int st_s2s_embed(const int* tok, const unsigned char* unk_mask, int B, int Tt, i
   return (int)hipGetLastError();
 }
 
-int st_s2s_decode(const float* gin, const float* wc_t, const float* wq_t, const float* wloc_t, const float* wd,
-                  const float* v, const float* mem, const float* pmem, const unsigned char* mask, int B, int L, int steps,
-                  float* attn, float* hc, hipStream_t s) {
+namespace {
+template <bool SAVE>
+int s2s_decode_launch(const float* gin, const float* wc_t, const float* wq_t, const float* wloc_t, const float* wd,
+                      const float* v, const float* mem, const float* pmem, const unsigned char* mask, int B, int L,
+                      int steps, float* attn, float* hc, float* sv_gates, float* sv_cell, float* sv_cum,
+                      hipStream_t s) {
   if (!gin || !wc_t || !wq_t || !wloc_t || !wd || !v || !mem || !pmem || !hc) return ST_EINVAL;
   if (B <= 0 || L <= 0 || L > ST_ALIGNER_MAX_L || steps <= 0) return ST_EINVAL;
-  const int Lr = (L + DTL - 1) / DTL * DTL;
-  const size_t lds = ((size_t)2 * (Lr + 2 * DP) + L) * sizeof(float);
+  const size_t lds = ((size_t)2 * padded(L) + L) * sizeof(float);
   static std::mutex mu;
   static bool raised = false;
   {
     std::lock_guard<std::mutex> lk(mu);
     if (!raised) {  // the longest utterances need more than the default 64 KB of LDS per workgroup
-      const size_t lmax = ((size_t)2 * (ST_ALIGNER_MAX_L + 2 * DP) + ST_ALIGNER_MAX_L) * sizeof(float);
-      ST_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_s2s_decode),
+      const size_t lmax = ((size_t)2 * padded(ST_ALIGNER_MAX_L) + ST_ALIGNER_MAX_L) * sizeof(float);
+      ST_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_s2s_decode<SAVE>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lmax));
       raised = true;
     }
   }
-  hipLaunchKernelGGL(k_s2s_decode, dim3((unsigned)B), dim3(DT), lds, s, gin, wc_t, wq_t, wloc_t, wd, v, mem, pmem, mask,
-                     L, steps, attn, hc);
+  hipLaunchKernelGGL(k_s2s_decode<SAVE>, dim3((unsigned)B), dim3(DT), lds, s, gin, wc_t, wq_t, wloc_t, wd, v, mem, pmem,
+                     mask, L, steps, attn, hc, sv_gates, sv_cell, sv_cum);
   return (int)hipGetLastError();
+}
+}  // namespace
+
+int st_s2s_decode(const float* gin, const float* wc_t, const float* wq_t, const float* wloc_t, const float* wd,
+                  const float* v, const float* mem, const float* pmem, const unsigned char* mask, int B, int L, int steps,
+                  float* attn, float* hc, hipStream_t s) {
+  return s2s_decode_launch<false>(gin, wc_t, wq_t, wloc_t, wd, v, mem, pmem, mask, B, L, steps, attn, hc, nullptr,
+                                  nullptr, nullptr, s);
+}
+
+int st_s2s_decode_train(const float* gin, const float* wc_t, const float* wq_t, const float* wloc_t, const float* wd,
+                        const float* v, const float* mem, const float* pmem, const unsigned char* mask, int B, int L,
+                        int steps, float* attn, float* hc, float* sv_gates, float* sv_cell, float* sv_cum,
+                        hipStream_t s) {
+  if (!attn || !sv_gates || !sv_cell || !sv_cum) return ST_EINVAL;
+  return s2s_decode_launch<true>(gin, wc_t, wq_t, wloc_t, wd, v, mem, pmem, mask, B, L, steps, attn, hc, sv_gates,
+                                 sv_cell, sv_cum, s);
 }
 
 long long st_max_path_workspace_bytes(int B, int Tx, int Ty) {

@@ -331,6 +331,15 @@ int st_s2s_embed(const int* tok, const unsigned char* unk_mask, int B, int Tt, i
 int st_s2s_decode(const float* gin, const float* wc_t, const float* wq_t, const float* wloc_t, const float* wd,
                   const float* v, const float* mem, const float* pmem, const unsigned char* mask, int B, int L, int steps,
                   float* attn, float* hc, hipStream_t s);
+// the same recurrence (the same kernel body) that also stores, per step, the gate activations sv_gates [B][steps][512]
+// (i, f, g, o), the cell state sv_cell [B][steps][128] and the cumulative weights before the step sv_cum [B][steps][L]
+int st_s2s_decode_train(const float* gin, const float* wc_t, const float* wq_t, const float* wloc_t, const float* wd,
+                        const float* v, const float* mem, const float* pmem, const unsigned char* mask, int B, int L,
+                        int steps, float* attn, float* hc, float* sv_gates, float* sv_cell, float* sv_cum,
+                        hipStream_t s);
+// frames the S2S backward's workgroup holds in LDS (aligner_train.hip): five [L] arrays (82.9 KB at the cap) next to
+// 60.7 KB of tiles and state, within the 160 KiB of a CU
+constexpr int ST_S2S_BWD_MAX_L = 4096;
 // monotonic alignment search: value [B][Tx][Ty], HOST lengths -> path [B][Tx][Ty] of 0 / 1
 long long st_max_path_workspace_bytes(int B, int Tx, int Ty);
 int st_max_path(const float* value, const int* tx_len, const int* ty_len, int B, int Tx, int Ty, float* path, void* ws,

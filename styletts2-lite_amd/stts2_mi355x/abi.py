@@ -181,4 +181,13 @@ SIGNATURES = {
     "stts_padl_add_bwd": ([vp, i, i, i, vp, vp], i),
     "stts_cistft_head_fwd": ([vp, vp, vp, i, i, i, i, vp, vp], i),
     "stts_cistft_head_bwd": ([vp, vp, vp, vp, i, i, i, i, vp, vp], i),
+    # the aligner's S2S decoder under training, loss_s2s, loss_mono (params / grads: host arrays of 14 pointers)
+    "stts_s2s_save_bytes": ([i, i, i], ll),
+    "stts_s2s_fwd_train_workspace_bytes": ([i, i, i, i, i], ll),
+    "stts_s2s_fwd_train": ([vp, vp, vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp, ll, vp], i),
+    "stts_s2s_bwd_workspace_bytes": ([i, i, i, i, i], ll),
+    "stts_s2s_bwd": ([vp, vp, vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ll, vp], i),
+    "stts_s2s_loss_workspace_bytes": ([i], ll),
+    "stts_s2s_loss": ([vp, ll, ll, i, i, i, vp, ll, vp, vp, vp, vp, vp, ll, vp], i),
+    "stts_mono_loss": ([vp, vp, ll, vp, vp, vp, vp], i),
 }

@@ -4,14 +4,18 @@ train.py opens every iteration with `ppgs, s2s_pred, s2s_attn = model.text_align
 :381 in validation).  This module holds the reference's 143 state-dict entries (so `load_state_dict(strict=True)`
 takes a checkpoint's `text_aligner` block) and runs the eval-mode forward under no_grad on the HIP plan
 (engine.AlignerEngine -> stts_aligner_fwd): the conv stack on the conv engines, the S2S attention decoder's
-Tt + 1 steps as one persistent launch.  Training the aligner (its backward, loss_s2s / loss_mono, its optimizer
-step, train-mode dropout) is not built: train mode raises.
+Tt + 1 steps as one persistent launch.
+
+ASRS2S, the attention decoder, is trainable on its own: ASRS2S.forward runs stts_s2s_fwd_train / stts_s2s_bwd (back-
+propagation through time in one persistent launch) under autograd, with losses.s2s_loss and losses.mono_loss.  The
+conv stack's backward is not built, so ASRCNN in train mode still raises, and TrainStep does not step the aligner.
 
 `to_mfcc.dct_mat` is torchaudio's create_dct(40, 80, 'ortho'), computed here from its formula (torchaudio is not a
 dependency); after load_state_dict the checkpoint's own buffer runs.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 
 import torch
@@ -98,6 +102,96 @@ class ASRS2S(nn.Module):
         self.decoder_rnn = nn.LSTMCell(hidden_dim + embedding_dim, hidden_dim)
         self.project_to_hidden = nn.Sequential(LinearNorm(hidden_dim * 2, hidden_dim), nn.Tanh())
         self.sos, self.eos, self.unk_index, self.random_mask = 1, 2, 3, 0.1
+        self.n_token, self.embedding_dim = n_token, embedding_dim
+
+    def forward(self, memory, memory_mask, text_input, unk_mask=None):
+        """reference models.py:118-147: memory [B, L, 128], memory_mask bool [B, L] (True = padded) or None,
+        text_input [B, Tt] -> (hidden [B, Tt + 1, 128], logit [B, Tt + 1, n_token], alignments [B, Tt + 1, L]).
+        With grad mode on and a parameter or `memory` requiring grad, the autograd path (all three outputs take
+        upstream gradients); in train mode F.dropout(hidden, 0.5) of :174 is training.dropout (device counter draws,
+        or the masks of training.set_dropout_masks).  unk_mask (bool [B, Tt]): the tokens replaced by the unknown
+        index, drawn on the host as the reference does when None."""
+        from .texttrain import needs_grad
+        if self.decoder_rnn_dim != 128 or self.attention_layer.location_layer.location_conv.conv.weight.shape != (
+                32, 2, 63):
+            raise NotImplementedError("ASRS2S: the HIP decoder is built for hidden_dim = 128, 32 location filters of "
+                                      "63 taps (the reference's)")
+        tok = text_input.detach().cpu()
+        if tok.dim() != 2 or tok.shape[1] < 1:
+            raise ValueError(f"ASRS2S: text_input must be [B, Tt >= 1], got {tuple(tok.shape)}")
+        if int(tok.min()) < 0 or int(tok.max()) >= self.n_token:
+            raise IndexError(f"ASRS2S: token indices must lie in [0, {self.n_token})")
+        if unk_mask is None:
+            unk_mask = torch.rand(text_input.shape) < self.random_mask
+        dev = memory.device
+        B, L, _ = memory.shape
+        steps = tok.shape[1] + 1
+        scale = None
+        if self.training:
+            from .training import dropout
+            scale = dropout(torch.ones(B, steps, 128, dtype=torch.float32, device=dev), 0.5).detach()
+        um = unk_mask.to(device=dev, dtype=torch.uint8).contiguous()
+        mm = None if memory_mask is None else memory_mask.to(device=dev, dtype=torch.uint8).contiguous()
+        tk = tok.to(device=dev, dtype=torch.int32).contiguous()
+        params = [p for _, p in self.named_parameters()]
+        if needs_grad(self, memory):
+            return _S2SFn.apply(memory, mm, tk, um, scale, *params)
+        with torch.no_grad():
+            return _s2s_forward(memory, mm, tk, um, scale, params, save=False)[:3]
+
+
+def _s2s_forward(memory, mm, tk, um, scale, params, save):
+    from .engine import _require_device, call, query
+    _require_device()
+    mc = memory.detach().to(torch.float32).contiguous()
+    ps = [p.detach().to(torch.float32).contiguous() for p in params]
+    B, L, D = mc.shape
+    Tt = tk.shape[1]
+    ntok, E = ps[0].shape
+    if D != 128 or len(ps) != 14:
+        raise ValueError(f"ASRS2S: memory must be [B, L, 128], got {tuple(mc.shape)}")
+    dev = mc.device
+    hidden = torch.empty(B, Tt + 1, D, dtype=torch.float32, device=dev)
+    logit = torch.empty(B, Tt + 1, ntok, dtype=torch.float32, device=dev)
+    attn = torch.empty(B, Tt + 1, L, dtype=torch.float32, device=dev)
+    sv = torch.empty(query("stts_s2s_save_bytes", B, L, Tt), dtype=torch.uint8, device=dev) if save else None
+    arr = (ctypes.c_void_p * 14)(*[p.data_ptr() for p in ps])
+    call("stts_s2s_fwd_train", mc, mm, tk, um, arr, B, L, Tt, ntok, E, scale, hidden, logit, attn, sv,
+         ws=("stts_s2s_fwd_train_workspace_bytes", B, L, Tt, ntok, E))
+    return hidden, logit, attn, sv, mc, ps
+
+
+class _S2SFn(torch.autograd.Function):
+    """ASRS2S.forward with its backward: stts_s2s_fwd_train / stts_s2s_bwd.  Inputs after the five data tensors: the
+    14 parameters in named_parameters() order."""
+
+    @staticmethod
+    def forward(ctx, memory, mm, tk, um, scale, *params):
+        hidden, logit, attn, sv, mc, ps = _s2s_forward(memory, mm, tk, um, scale, params, save=True)
+        none = torch.empty(0)
+        ctx.save_for_backward(mc, mm if mm is not None else none, tk, um, scale if scale is not None else none,
+                              hidden, attn, sv, *ps)
+        ctx.has = (mm is not None, scale is not None)
+        return hidden, logit, attn
+
+    @staticmethod
+    def backward(ctx, dhidden, dlogit, dattn):
+        from .engine import call
+        mc, mm, tk, um, scale, hidden, attn, sv, *ps = ctx.saved_tensors
+        mm = mm if ctx.has[0] else None
+        scale = scale if ctx.has[1] else None
+        B, L, D = mc.shape
+        Tt = tk.shape[1]
+        ntok, E = ps[0].shape
+        need = ctx.needs_input_grad
+        f32 = lambda t: None if t is None else t.to(torch.float32).contiguous()  # noqa: E731
+        dmem = torch.empty_like(mc) if need[0] else None
+        grads = [torch.empty_like(p) if need[5 + i] else None for i, p in enumerate(ps)]
+        arr = (ctypes.c_void_p * 14)(*[p.data_ptr() for p in ps])
+        garr = (ctypes.c_void_p * 14)(*[g.data_ptr() if g is not None else None for g in grads])
+        call("stts_s2s_bwd", mc, mm, tk, um, arr, B, L, Tt, ntok, E, scale, hidden, attn, sv, f32(dhidden),
+             f32(dlogit), f32(dattn), dmem, garr, ws=("stts_s2s_bwd_workspace_bytes", B, L, Tt, ntok, E))
+        return (dmem, None, None, None, None, *grads)
 
 
 class ASRCNN(nn.Module):
@@ -131,8 +225,9 @@ class ASRCNN(nn.Module):
 
     def _check(self):
         if self.training:
-            raise NotImplementedError("ASRCNN: the HIP path is the eval-mode forward under no_grad (no dropout, no "
-                                      "backward: training the aligner is not built); call .eval() first")
+            raise NotImplementedError("ASRCNN: the HIP path is the eval-mode forward under no_grad; the conv stack's "
+                                      "backward (GroupNorm, ConvBlock dropout) is not built, only asr_s2s trains "
+                                      "(ASRS2S.forward); call .eval() first")
         if self.cfg[0] != 80 or self.cfg[1] != 256:
             raise NotImplementedError("ASRCNN: the HIP plan is built for input_dim = 80, hidden_dim = 256 (the "
                                       "reference's)")

@@ -232,12 +232,13 @@ def symbol_table(config):
     return table, len(table) + 1
 
 
-def build_models(config, pitch_extractor=False):
+def build_models(config, pitch_extractor=False, text_aligner=False):
     """inference.py:88-122 with the drop-in classes: the parsed config.yaml (a dict) ->
     {'decoder', 'predictor', 'text_encoder', 'style_encoder'} modules (parameters on the CPU,
     move them with .to('cuda')).  pitch_extractor=True adds the training step's frozen
     'pitch_extractor' (jdc.JDCNet from config['model_params']['JDC_params'], models.py build_model), which
-    load_models then fills from the checkpoint's entry of that name."""
+    load_models then fills from the checkpoint's entry of that name; text_aligner=True adds 'text_aligner'
+    (asr.ASRCNN from config['model_params']['ASR_params'] and the symbol table's n_token, models.py:568-569) in the same way."""
     from . import hifigan, istftnet, vocos
     from .models import ProsodyPredictor, StyleEncoder, TextEncoder
     args = config["model_params"]
@@ -272,6 +273,11 @@ def build_models(config, pitch_extractor=False):
         from .jdc import JDCNet
         jdc = args["JDC_params"]
         models["pitch_extractor"] = JDCNet(num_class=jdc["num_class"], seq_len=jdc["seq_len"])
+    if text_aligner:
+        from .asr import ASRCNN
+        a = args["ASR_params"]
+        models["text_aligner"] = ASRCNN(input_dim=a["input_dim"], hidden_dim=a["hidden_dim"], n_token=n_token,
+                                        n_layers=a["n_layers"], token_embedding_dim=a["token_embedding_dim"])
     return models
 
 

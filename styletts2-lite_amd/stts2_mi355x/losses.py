@@ -252,3 +252,77 @@ def smooth_l1_loss(x, y):
     """F.smooth_l1_loss(x, y) as train.py:269-270 calls it (loss_F0_rec = smooth_l1(F0_real, F0_fake) / 10,
     loss_norm_rec = smooth_l1(N_real, N_fake))."""
     return _SmoothL1Fn.apply(x, y)
+
+
+class _S2SLossFn(torch.autograd.Function):
+    """loss_s2s (train.py:301-304): value and gradient in one launch (stts_s2s_loss)."""
+
+    @staticmethod
+    def forward(ctx, pred, texts, ln):
+        _require_device()
+        pc = pred if pred.stride(-1) == 1 and pred.dtype == torch.float32 else _c(pred)
+        B, T, K = pc.shape
+        tok = texts.to(device=pc.device, dtype=torch.int64)
+        if tok.stride(-1) != 1:
+            tok = tok.contiguous()
+        loss = torch.empty(1, dtype=torch.float64, device=pc.device)
+        call("stts_s2s_loss", pc, pc.stride(0), pc.stride(1), B, T, K, tok, tok.stride(0), ln, loss, None, None,
+             ws=("stts_s2s_loss_workspace_bytes", B))
+        ctx.save_for_backward(pc, tok, ln)
+        return loss[0].to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, g):
+        pc, tok, ln = ctx.saved_tensors
+        B, T, K = pc.shape
+        loss = torch.empty(1, dtype=torch.float64, device=pc.device)
+        dz = torch.empty(B, T, K, dtype=torch.float32, device=pc.device)
+        call("stts_s2s_loss", pc, pc.stride(0), pc.stride(1), B, T, K, tok, tok.stride(0), ln, loss, dz,
+             _c(g.reshape(1)), ws=("stts_s2s_loss_workspace_bytes", B))
+        return dz, None, None
+
+
+def s2s_loss(s2s_pred, texts, input_lengths):
+    """train.py:301-304: mean over the batch of cross_entropy(s2s_pred[b, :len_b], texts[b, :len_b]).  s2s_pred
+    [B, T, n_token] with T >= max(len); texts [B, >= max(len)] integer tokens inside the table (IndexError
+    otherwise, before any launch)."""
+    ln_host = torch.as_tensor(input_lengths).detach().cpu().to(torch.int64)
+    tk = torch.as_tensor(texts).detach().cpu()
+    B, T, K = s2s_pred.shape
+    if ln_host.numel() != B or int(ln_host.max()) > min(T, tk.shape[1]) or int(ln_host.min()) < 0:
+        raise ValueError(f"s2s_loss: lengths {ln_host.tolist()} for logits {tuple(s2s_pred.shape)}, "
+                         f"texts {tuple(tk.shape)}")
+    for b in range(B):
+        row = tk[b, :int(ln_host[b])]
+        if row.numel() and (int(row.min()) < 0 or int(row.max()) >= K):
+            raise IndexError(f"s2s_loss: token indices must lie in [0, {K})")
+    ln = ln_host.to(device=s2s_pred.device, dtype=torch.int32)
+    return _S2SLossFn.apply(s2s_pred, texts, ln)
+
+
+class _MonoLossFn(torch.autograd.Function):
+    """loss_mono (train.py:306): value and gradient in one launch (stts_mono_loss)."""
+
+    @staticmethod
+    def forward(ctx, attn, mono):
+        _require_device()
+        ac, mc = _c(attn), _c(mono)
+        if ac.shape != mc.shape:
+            raise ValueError(f"mono_loss: {tuple(ac.shape)} vs {tuple(mc.shape)}")
+        loss = torch.empty(1, dtype=torch.float64, device=ac.device)
+        call("stts_mono_loss", ac, mc, ac.numel(), loss, None, None)
+        ctx.save_for_backward(ac, mc)
+        return loss[0].to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, g):
+        ac, mc = ctx.saved_tensors
+        loss = torch.empty(1, dtype=torch.float64, device=ac.device)
+        da = torch.empty_like(ac)
+        call("stts_mono_loss", ac, mc, ac.numel(), loss, da, _c(g.reshape(1)))
+        return da, (-da if ctx.needs_input_grad[1] else None)
+
+
+def mono_loss(s2s_attn, s2s_attn_mono):
+    """train.py:306: F.l1_loss(s2s_attn, s2s_attn_mono) * 10."""
+    return _MonoLossFn.apply(s2s_attn, s2s_attn_mono)
