@@ -303,7 +303,9 @@ int stts_pool_bwd(const float* x, const float* w, const float* dy, int B, int Li
 int stts_upsample2(const float* x, int B, int Lin, int C, float* y, void* stream);
 int stts_upsample2_bwd(const float* dy, int B, int Lin, int C, float* dx, void* stream);
 /* LeakyReLU(slope) over n fp32 values and its backward from the output y (slope > 0), as the
- * discriminators apply it after every conv (discriminators.py:119, slope 0.1). */
+ * discriminators apply it after every conv (discriminators.py:119, slope 0.1).  The backward also takes slope 0,
+ * the ReLU a conv applied in its epilogue (stts_conv1d_fwd_act with slope 0, the text aligner's ConvBlock): where
+ * y = 0 the gradient is 0 either way, so the output's sign still decides. */
 int stts_leaky_relu(const float* x, long long n, float slope, float* y, void* stream);
 int stts_leaky_relu_bwd(const float* y, const float* dy, long long n, float slope, float* dx, void* stream);
 /* weight_norm backward (the training step's convs are weight-normed, hifigan.py:26-80): for w = g v / ||v||

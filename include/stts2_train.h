@@ -384,6 +384,42 @@ int stts_s2s_loss(const float* logits, long long ls_b, long long ls_t, int B, in
 int stts_mono_loss(const float* attn, const float* attn_mono, long long n, double* loss, float* dattn, const float* g,
                    void* stream);
 
+/* ---- The text aligner's conv stack under train.py's step (Modules/ASR/models.py ASRCNN :37-48, layers.py ConvBlock
+ * :105-131; csrc/aligner_cnn_train.hip).  fp32 frames [B][L][C]; every sum in a fixed order, no atomics.  The convs
+ * themselves (with their ReLU) are stts_conv1d_fwd_act / stts_conv1d_bwd.
+ *
+ * Dropout arguments (p, seed, keep_mask), the same in the four entry points that take them: p = 0 is the identity;
+ * with keep_mask (fp32, laid out as the tensor it applies to, 1 = kept) y = mask != 0 ? v / (1 - p) : 0, as
+ * stts_dropout_mask; otherwise flat element i is kept exactly when stts_dropout(seed) keeps element i of the same
+ * tensor, so a fused result is bitwise the unfused pair and a backward redraws instead of storing.  0 <= p < 1. */
+
+/* nn.GroupNorm(G, C) (eps 1e-5, biased variance) of v = relu ? max(x, 0) : x over each (utterance, group)'s C / G
+ * channels x L frames, then the dropout above:  y = dropout((v - mean) rstd w[c] + b[c]).  stats [B][G][2] keeps
+ * (mean, rstd) for the backward.  The L rows are cut into S row slices, S a function of L alone (16 rows each, at
+ * most 256): a workgroup per (64 channels, slice, utterance) writes fp64 partials, a second pass adds them in channel
+ * and slice order, so a batch row's y is bitwise its B = 1 result.  C % G == 0; B <= 65535.
+ * Workspace >= stts_groupnorm_fwd_train_workspace_bytes(B, L, C, G) = B S C 2 doubles rounded up to 256 bytes. */
+long long stts_groupnorm_fwd_train_workspace_bytes(int B, int L, int C, int G);
+int stts_groupnorm_fwd_train(const float* x, const float* w, const float* b, int B, int L, int C, int G, int relu,
+                             float p, unsigned long long seed, const float* keep_mask, float* y, float* stats,
+                             void* ws, long long ws_bytes, void* stream);
+/* Its backward from dy (the gradient of y, after the dropout): with g = dropout(dy), g' = g w[c],
+ * xhat = (v - mean) rstd, n = L C / G:  dv = rstd (g' - sum g' / n - xhat sum(g' xhat) / n),
+ * dx = relu ? dv (x > 0) : dv,  dw[c] = sum_{b,l} g xhat,  db[c] = sum_{b,l} g (utterances in ascending b).
+ * dx, dw, db are each nullable.  Same x, w, stats, relu and dropout arguments as the forward. */
+long long stts_groupnorm_bwd_workspace_bytes(int B, int L, int C, int G);
+int stts_groupnorm_bwd(const float* x, const float* w, const float* stats, const float* dy, int B, int L, int C, int G,
+                       int relu, float p, unsigned long long seed, const float* keep_mask, float* dx, float* dw,
+                       float* db, void* ws, long long ws_bytes, void* stream);
+/* The ConvBlock tail `x = block(x); x += res` (layers.py:116-118): y = r + dropout(x) over n >= 1 values.  Backward:
+ * dx = stts_dropout / stts_dropout_mask of dy, dr = dy itself. */
+int stts_dropout_add_fwd(const float* x, const float* r, long long n, float p, unsigned long long seed,
+                         const float* keep_mask, float* y, void* stream);
+/* MFCC.forward (layers.py:60-74): mel [B][n_mels][T], dct [n_mels][n_mfcc] (the module's dct_mat buffer) ->
+ * out frames [B][T][n_mfcc].  No backward: the mel is data and dct_mat a buffer. */
+int stts_mfcc_frames(const float* mel, const float* dct, int B, int n_mels, int T, int n_mfcc, float* out,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -605,7 +605,7 @@ extern "C" int stts_leaky_relu(const float* x, long long n, float slope, float* 
 
 extern "C" int stts_leaky_relu_bwd(const float* y, const float* dy, long long n, float slope, float* dx,
                                    void* stream) {
-  if (!y || !dy || !dx || n < 0 || !(slope > 0.f)) return ST_EINVAL;
+  if (!y || !dy || !dx || n < 0 || !(slope >= 0.f)) return ST_EINVAL;  // (0: the ReLU of a conv epilogue)
   if (n == 0) return 0;
   hipLaunchKernelGGL(k_lrelu_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, y, dy, n,
                      slope, dx);

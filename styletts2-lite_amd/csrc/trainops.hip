@@ -14,6 +14,7 @@
 #include "../../include/stts2.h"
 #include "../../include/stts2_train.h"
 #include "common.h"
+#include "dropout_draw.h"
 #include "kernels.h"
 
 namespace {
@@ -565,10 +566,9 @@ __global__ void k_adamw_prep(double* __restrict__ st, double lr, double beta1, d
 
 // ------------------------------------------------------------------ Dropout (train mode)
 // keep element i when its counter draw u(seed, i) >= p; y = keep ? x / (1 - p) : 0 (torch's scaling).  The
-// backward redraws the same mask from (seed, i): nothing is stored.
+// backward redraws the same mask from (seed, i): nothing is stored.  The draw itself is dropout_draw.h's.
 __device__ __forceinline__ bool drop_keep(unsigned long long seed, long long i, float p) {
-  const unsigned long long z = splitmix64(seed ^ splitmix64((unsigned long long)i * 0xD1B54A32D192ED03ULL));
-  return (float)(z >> 40) * (1.0f / 16777216.0f) >= p;
+  return drop::keep(seed, i, p);
 }
 
 __global__ void __launch_bounds__(256) k_dropout(const float* __restrict__ x, long long n, float p, float scale,

@@ -190,4 +190,11 @@ SIGNATURES = {
     "stts_s2s_loss_workspace_bytes": ([i], ll),
     "stts_s2s_loss": ([vp, ll, ll, i, i, i, vp, ll, vp, vp, vp, vp, vp, ll, vp], i),
     "stts_mono_loss": ([vp, vp, ll, vp, vp, vp, vp], i),
+    # the aligner's conv stack under training: GroupNorm with kept statistics, dropout + residual, MFCC frames
+    "stts_groupnorm_fwd_train_workspace_bytes": ([i, i, i, i], ll),
+    "stts_groupnorm_fwd_train": ([vp, vp, vp, i, i, i, i, i, f, ull, vp, vp, vp, vp, ll, vp], i),
+    "stts_groupnorm_bwd_workspace_bytes": ([i, i, i, i], ll),
+    "stts_groupnorm_bwd": ([vp, vp, vp, vp, i, i, i, i, i, f, ull, vp, vp, vp, vp, vp, ll, vp], i),
+    "stts_dropout_add_fwd": ([vp, vp, ll, f, ull, vp, vp, vp], i),
+    "stts_mfcc_frames": ([vp, vp, i, i, i, i, vp, vp], i),
 }

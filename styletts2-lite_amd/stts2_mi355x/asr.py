@@ -7,8 +7,14 @@ takes a checkpoint's `text_aligner` block) and runs the eval-mode forward under 
 Tt + 1 steps as one persistent launch.
 
 ASRS2S, the attention decoder, is trainable on its own: ASRS2S.forward runs stts_s2s_fwd_train / stts_s2s_bwd (back-
-propagation through time in one persistent launch) under autograd, with losses.s2s_loss and losses.mono_loss.  The
-conv stack's backward is not built, so ASRCNN in train mode still raises, and TrainStep does not step the aligner.
+propagation through time in one persistent launch) under autograd, with losses.s2s_loss and losses.mono_loss.
+
+The whole aligner trains when built with `ASRCNN(..., trainable=True)`: in train mode forward runs the same structure
+as a composition under autograd (ASRCNN._features: the convs on training.conv1d_frames, GroupNorm with kept
+statistics and the ConvBlock dropouts on stts_groupnorm_fwd_train / _bwd and stts_dropout_add_fwd, ctc_linear as K = 1
+convs, the projection output handed to ASRS2S.forward as `memory`), and TrainStep(train_aligner=True) steps it.  The
+keyword is opt-in: a default-built ASRCNN in train mode still raises (tests/test_aligner_cpu.py pins that), and in
+eval mode both run the plan under no_grad, bit for bit alike.  Flipping the default is a later change.
 
 `to_mfcc.dct_mat` is torchaudio's create_dct(40, 80, 'ortho'), computed here from its formula (torchaudio is not a
 dependency); after load_state_dict the checkpoint's own buffer runs.
@@ -195,12 +201,15 @@ class _S2SFn(torch.autograd.Function):
 
 
 class ASRCNN(nn.Module):
-    """reference Modules/ASR/models.py:8-72."""
+    """reference Modules/ASR/models.py:8-72.  `trainable=True` (a constructor keyword, not part of the state dict)
+    allows train mode: forward and get_feature then run the autograd composition (_features) instead of the plan."""
 
-    def __init__(self, input_dim=80, hidden_dim=256, n_token=35, n_layers=6, token_embedding_dim=256):
+    def __init__(self, input_dim=80, hidden_dim=256, n_token=35, n_layers=6, token_embedding_dim=256,
+                 trainable=False):
         super().__init__()
         self.n_token = n_token
         self.n_down = 1
+        self.trainable = bool(trainable)
         self.cfg = [input_dim, hidden_dim, n_token, n_layers, token_embedding_dim]
         self.to_mfcc = MFCC()
         self.init_cnn = ConvNorm(input_dim // 2, hidden_dim, kernel_size=7, padding=3, stride=2)
@@ -224,13 +233,49 @@ class ASRCNN(nn.Module):
         return self._engine
 
     def _check(self):
-        if self.training:
-            raise NotImplementedError("ASRCNN: the HIP path is the eval-mode forward under no_grad; the conv stack's "
-                                      "backward (GroupNorm, ConvBlock dropout) is not built, only asr_s2s trains "
-                                      "(ASRS2S.forward); call .eval() first")
+        if self.training and not self.trainable:
+            raise NotImplementedError("ASRCNN: built with trainable=False, the HIP path is the eval-mode forward under "
+                                      "no_grad; build it with ASRCNN(..., trainable=True) to run train mode (the "
+                                      "autograd composition), or call .eval() first")
         if self.cfg[0] != 80 or self.cfg[1] != 256:
             raise NotImplementedError("ASRCNN: the HIP plan is built for input_dim = 80, hidden_dim = 256 (the "
                                       "reference's)")
+
+    def _features(self, x, dtype="fp32"):
+        """Train mode (trainable=True): mel [B, 80, T] -> the projection output as frames [B, L, 128], the eval
+        plan's structure (plan.cpp:aligner_forward) as a composition under autograd: MFCC, init_cnn, 6 x [3 x
+        (conv + ReLU -> GroupNorm(8) + dropout -> conv + ReLU -> dropout + input) -> GroupNorm(1)], projection.  A
+        ConvBlock entry is four launches forward (training.conv1d_frames with act_slope 0, group_norm_frames,
+        dropout_add).  The 36 dropouts are drawn on the device, or taken from training.set_dropout_masks in the
+        reference's call order and [B, 256, L] layout.  The mel gets no gradient: it is data (stts_mfcc_frames has no
+        backward)."""
+        from . import training as Tr
+        if dtype != "fp32":
+            raise NotImplementedError("ASRCNN: train mode runs in fp32")
+        if not x.is_cuda:
+            raise RuntimeError("ASRCNN: train mode needs the input on a HIP device; no CPU fallback exists")
+        h = Tr.mfcc_frames(x, self.to_mfcc.dct_mat)
+        c = self.init_cnn.conv
+        h = Tr.conv1d_frames(h, c.weight, c.bias, stride=2, padding=3)
+        for layer in self.cnns:
+            for blk in layer[0].blocks:
+                c1, gn, c2 = blk[0].conv, blk[2], blk[4].conv
+                t = Tr.conv1d_frames(h, c1.weight, c1.bias, padding=c1.padding[0], dilation=c1.dilation[0],
+                                     act_slope=0.0)
+                t = Tr.group_norm_frames(t, gn.weight, gn.bias, gn.num_groups, p=blk[3].p, ref_transpose=True)
+                t = Tr.conv1d_frames(t, c2.weight, c2.bias, padding=c2.padding[0], act_slope=0.0)
+                h = Tr.dropout_add(t, h, blk[6].p, ref_transpose=True)
+            gn = layer[1]
+            h = Tr.group_norm_frames(h, gn.weight, gn.bias, gn.num_groups)
+        c = self.projection.conv
+        return Tr.conv1d_frames(h, c.weight, c.bias)
+
+    def _ctc(self, feat):
+        """ctc_linear (Linear, ReLU, Linear) over frames [B, L, 128] as K = 1 convs."""
+        from . import training as Tr
+        l1, l2 = self.ctc_linear[0].linear_layer, self.ctc_linear[2].linear_layer
+        h = Tr.conv1d_frames(feat, l1.weight.unsqueeze(-1), l1.bias, act_slope=0.0)
+        return Tr.conv1d_frames(h, l2.weight.unsqueeze(-1), l2.bias)
 
     def draw_unk_mask(self, text_input):
         """models.py:126: the 10 % unknown-token draw, on the host as the reference's, so torch.manual_seed
@@ -240,8 +285,19 @@ class ASRCNN(nn.Module):
     def forward(self, x, src_key_padding_mask=None, text_input=None, dtype="fp32", unk_mask=None):
         """mel [B, 80, T] -> ctc_logit [B, L, n_token], or with text_input [B, Tt] (ctc_logit, s2s_logit
         [B, Tt + 1, n_token], s2s_attn [B, Tt + 1, L]); L = ceil(T / 2).  unk_mask (bool [B, Tt]): the tokens
-        replaced by the unknown index, drawn as the reference does when None."""
+        replaced by the unknown index, drawn as the reference does when None.  In train mode (trainable=True) the
+        outputs carry the autograd graph of _features, ctc_linear and ASRS2S.forward (the projection output is the
+        decoder's `memory`, so its dmemory flows back into the conv stack); eval mode runs the plan under no_grad."""
         self._check()
+        if self.training:
+            feat = self._features(x, dtype)
+            ctc = self._ctc(feat)
+            if text_input is None:
+                return ctc
+            if unk_mask is None:
+                unk_mask = self.draw_unk_mask(text_input)
+            _, s2s, attn = self.asr_s2s(feat, src_key_padding_mask, text_input, unk_mask=unk_mask)
+            return ctc, s2s, attn
         if text_input is None:
             with torch.no_grad():
                 return self.engine(dtype).forward(x, s2s=False, attn=False)[0]
@@ -257,6 +313,8 @@ class ASRCNN(nn.Module):
     def get_feature(self, x, dtype="fp32"):
         """The projection output [B, 128, L] (models.py:50-55)."""
         self._check()
+        if self.training:
+            return self._features(x.squeeze(1) if x.dim() == 4 else x, dtype).transpose(1, 2)
         with torch.no_grad():
             return self.engine(dtype).forward(x.squeeze(1) if x.dim() == 4 else x, ctc=False, feature=True)[3]
 

@@ -1495,20 +1495,133 @@ def set_dropout_masks(fn):
     _MASKS["fn"], _MASKS["k"] = fn, 0
 
 
-def dropout(x, p, ref_transpose=False):
-    """nn.Dropout(p) / F.dropout in train mode.  ref_transpose: the reference holds this tensor as x.transpose(1, 2)
-    (the TextEncoder's CNN, channels-first there), which is where an injected mask is laid out."""
-    if p <= 0:
-        return x
+def _next_mask(x, p, ref_transpose):
+    """The injected keep mask of the next train-mode dropout call, laid out as x (None: the device counter draws)."""
     fn = _MASKS["fn"]
     if fn is None:
-        return _DropoutFn.apply(x, float(p))
+        return None
     shape = tuple(x.transpose(1, 2).shape) if ref_transpose else tuple(x.shape)
     m = torch.as_tensor(fn(_MASKS["k"], shape, float(p)), dtype=torch.float32, device=x.device)
     _MASKS["k"] += 1
     if ref_transpose:
         m = m.transpose(1, 2)
-    return _DropoutMaskFn.apply(x, m.contiguous(), float(p))
+    return m.contiguous()
+
+
+def dropout(x, p, ref_transpose=False):
+    """nn.Dropout(p) / F.dropout in train mode.  ref_transpose: the reference holds this tensor as x.transpose(1, 2)
+    (the TextEncoder's CNN, channels-first there), which is where an injected mask is laid out."""
+    if p <= 0:
+        return x
+    m = _next_mask(x, p, ref_transpose)
+    if m is None:
+        return _DropoutFn.apply(x, float(p))
+    return _DropoutMaskFn.apply(x, m, float(p))
+
+
+# ------------------------------------------------------------------ the text aligner's conv stack (asr.ASRCNN)
+def _drop_args(x, p, ref_transpose):
+    """(p, seed, mask) of a fused train-mode dropout: the injected mask of this call, or a seed from torch's default
+    generator for the counter draws (what _DropoutFn draws, so torch.manual_seed governs both)."""
+    p = float(p)
+    if p <= 0:
+        return 0.0, 0, None
+    m = _next_mask(x, p, ref_transpose)
+    return p, (0 if m is not None else int(torch.randint(0, 2 ** 62, (1,)).item())), m
+
+
+class _GroupNormFn(torch.autograd.Function):
+    """dropout(GroupNorm(G)([ReLU] x)) on frames [B, L, C] with its backward: stts_groupnorm_fwd_train / _bwd.  The
+    statistics are kept; the dropout is redrawn from the seed (or re-read from the injected mask) by the backward."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, G, relu, p, seed, mask):
+        _require_device()
+        xc, wc, bc = _c(x), _c(w), _c(b)
+        B, L, C = xc.shape
+        if mask is not None and mask.shape != xc.shape:
+            raise ValueError(f"dropout mask {tuple(mask.shape)} for a tensor {tuple(xc.shape)}")
+        y = torch.empty_like(xc)
+        stats = torch.empty(B, G, 2, dtype=torch.float32, device=xc.device)
+        call("stts_groupnorm_fwd_train", xc, wc, bc, B, L, C, G, int(relu), p, seed, mask, y, stats,
+             ws=("stts_groupnorm_fwd_train_workspace_bytes", B, L, C, G))
+        ctx.save_for_backward(xc, wc, stats, mask)
+        ctx.cfg = (G, int(relu), p, seed)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        xc, wc, stats, mask = ctx.saved_tensors
+        G, relu, p, seed = ctx.cfg
+        B, L, C = xc.shape
+        dy = _c(gy)
+        nx, nw, nb = ctx.needs_input_grad[:3]
+        dx = torch.empty_like(xc) if nx else None
+        dw = torch.empty(C, dtype=torch.float32, device=dy.device) if nw else None
+        db = torch.empty(C, dtype=torch.float32, device=dy.device) if nb else None
+        call("stts_groupnorm_bwd", xc, wc, stats, dy, B, L, C, G, relu, p, seed, mask, dx, dw, db,
+             ws=("stts_groupnorm_bwd_workspace_bytes", B, L, C, G))
+        return dx, dw, db, None, None, None, None, None
+
+
+def group_norm_frames(x, weight, bias, num_groups, relu=False, p=0.0, ref_transpose=False):
+    """nn.GroupNorm(num_groups, C) of [ReLU of] frames x [B, L, C], then train-mode dropout(p) in the same launch
+    (p = 0: none).  ref_transpose as for dropout()."""
+    p, seed, m = _drop_args(x, p, ref_transpose)
+    return _GroupNormFn.apply(x, weight, bias, int(num_groups), bool(relu), p, seed, m)
+
+
+class _DropoutAddFn(torch.autograd.Function):
+    """y = r + dropout(x) (stts_dropout_add_fwd); backward: dx = the same dropout of dy, dr = dy itself."""
+
+    @staticmethod
+    def forward(ctx, x, r, p, seed, mask):
+        _require_device()
+        xc, rc = _c(x), _c(r)
+        if rc.shape != xc.shape or (mask is not None and mask.shape != xc.shape):
+            raise ValueError(f"dropout + residual: x {tuple(xc.shape)}, r {tuple(rc.shape)}")
+        y = torch.empty_like(xc)
+        call("stts_dropout_add_fwd", xc, rc, xc.numel(), p, seed, mask, y)
+        ctx.save_for_backward(mask)
+        ctx.cfg = (p, seed)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        (mask,) = ctx.saved_tensors
+        p, seed = ctx.cfg
+        nx, nr = ctx.needs_input_grad[:2]
+        dx = None
+        if nx:
+            dy = _c(gy)
+            if p <= 0:
+                dx = dy
+            else:
+                dx = torch.empty_like(dy)
+                if mask is not None:
+                    call("stts_dropout_mask", dy, mask, dy.numel(), p, dx)
+                else:
+                    call("stts_dropout", dy, dy.numel(), p, seed, dx)
+        return dx, (gy if nr else None), None, None, None
+
+
+def dropout_add(x, r, p, ref_transpose=False):
+    """r + dropout(x, p) in train mode, one launch (the ConvBlock tail `x = block(x); x += res`)."""
+    p, seed, m = _drop_args(x, p, ref_transpose)
+    return _DropoutAddFn.apply(x, r, p, seed, m)
+
+
+def mfcc_frames(mel, dct_mat):
+    """MFCC.forward on the device: mel [B, n_mels, T], dct_mat [n_mels, n_mfcc] -> frames [B, T, n_mfcc].  No
+    gradient: the mel is data and dct_mat a buffer."""
+    _require_device()
+    mc, dc = _c(mel), _c(dct_mat)
+    B, nm, T = mc.shape
+    if dc.shape[0] != nm:
+        raise ValueError(f"mfcc: mel {tuple(mc.shape)} against dct_mat {tuple(dc.shape)}")
+    out = torch.empty(B, T, dc.shape[1], dtype=torch.float32, device=mc.device)
+    call("stts_mfcc_frames", mc, dc, B, nm, T, dc.shape[1], out)
+    return out
 
 
 # ------------------------------------------------------------------ ProsodyPredictor.F0Ntrain (models.py:448-461)

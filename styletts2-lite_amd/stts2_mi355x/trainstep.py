@@ -37,8 +37,13 @@ version, the caller's coin), d_gt = attn_mono.sum(-1) (:225), s = style_encoder(
 predictor(t_en, s, input_lengths, attn_mono) (:230-233), the per-utterance crops en / p_en / gt of mel_len frames at
 `starts` (:235-251; the caller draws them, as train.py's np.random.randint), then the step above with en, p_en, gt,
 plus lambda_dur loss_dur + lambda_ce loss_ce (:286-299, texttrain.duration_losses) in g_loss and AdamW on the text
-encoder after the backward (:327).  The aligner's own losses (loss_s2s, loss_mono) and its optimizer step belong to
-the text aligner, outside this path; the gradient of asr with respect to attn is left on attn when it requires grad.
+encoder after the backward (:327).  By default the aligner is frozen and its own losses stay outside the step; the
+gradient of asr with respect to attn is left on attn when it requires grad.  With `train_aligner=True` (the aligner an
+asr.ASRCNN(trainable=True) in train mode; the text= dict gives mel_input_length and no alignments) the step is
+train.py's whole G step: the aligner runs with gradients (:206; s2s_pred, and s2s_attn with the SOS step dropped; the
+search of :213-214 stays under no_grad), asr = t_en @ s2s_attn is differentiable when mono=False, g_loss gains
+lambda_mono loss_mono + lambda_s2s loss_s2s (:301-315, losses.mono_loss / s2s_loss; both are returned) and AdamW steps
+the aligner after the text encoder (:328) at lr_aligner (the general lr).  Eager only: with graph=True it raises.
 `graph=True` (the config-5 step: decoder + discriminators): the step is recorded once in a hipGraph and replayed;
 the host then issues one graph launch per step instead of ~5,000 kernel launches through Python autograd.  Every
 per-step host scalar lives on the device: the AdamW step counts (optim.AdamW(capturable=True), stts_adamw_step_dev)
@@ -73,10 +78,21 @@ class TrainStep:
     def __init__(self, decoder, mpd, msd, lr_dec=1e-5, lr_disc=1e-4, lambda_mel=5.0, lambda_gen=1.0, dtype="fp32",
                  freeze_d_in_g=True, capture=False, predictor=None, style_encoder=None, lr_pred=1e-4, lr_style=1e-5,
                  lambda_F0=1.0, lambda_norm=1.0, text_encoder=None, lr_text=1e-4, lambda_dur=1.0, lambda_ce=1.0,
-                 graph=False, pitch_extractor=None, text_aligner=None):
+                 graph=False, pitch_extractor=None, text_aligner=None, train_aligner=False, lr_aligner=1e-4,
+                 lambda_mono=1.0, lambda_s2s=1.0):
         self.decoder, self.mpd, self.msd = decoder, mpd, msd
         self.pitch_extractor = pitch_extractor  # frozen (train.py:260-261): no optimizer, no gradient
-        self.text_aligner = text_aligner  # frozen too (an asr.ASRCNN in eval mode; freeze_modules: text_aligner)
+        # frozen too by default (an asr.ASRCNN in eval mode; freeze_modules: text_aligner); train_aligner=True: an
+        # ASRCNN(trainable=True) in train mode, stepped as train.py:206, 301-315, 328
+        self.text_aligner = text_aligner
+        self.train_aligner = bool(train_aligner)
+        self.lambda_mono, self.lambda_s2s = float(lambda_mono), float(lambda_s2s)
+        if self.train_aligner:
+            if graph:
+                raise NotImplementedError("TrainStep(graph=True) records the config-5 step (decoder + "
+                                          "discriminators); train_aligner=True runs eagerly")
+            if text_aligner is None or not getattr(text_aligner, "trainable", False):
+                raise ValueError("TrainStep(train_aligner=True) needs text_aligner= an asr.ASRCNN(trainable=True)")
         self.predictor, self.style_encoder, self.text_encoder = predictor, style_encoder, text_encoder
         self.lambda_dur, self.lambda_ce = float(lambda_dur), float(lambda_ce)
         self.lambda_F0, self.lambda_norm = float(lambda_F0), float(lambda_norm)
@@ -102,6 +118,8 @@ class TrainStep:
             self.opt["style_encoder"] = mk(style_encoder, lr_style)
         if text_encoder is not None:  # train.py:137-157: the text encoder at the general lr
             self.opt["text_encoder"] = mk(text_encoder, lr_text)
+        if self.train_aligner:  # the text aligner at the general lr as well
+            self.opt["text_aligner"] = mk(text_aligner, lr_aligner)
         self.lambda_mel, self.lambda_gen = float(lambda_mel), float(lambda_gen)
         self.freeze_d_in_g = freeze_d_in_g
 
@@ -210,6 +228,23 @@ class TrainStep:
             mask_ST = mask_from_lens(s2s_attn, torch.as_tensor(input_lengths), half)
             return s2s_attn, maximum_path(s2s_attn, mask_ST)
 
+    def _align_train(self, mels, mel_input_length, texts, input_lengths, unk_mask=None):
+        """train.py:203-214 with the aligner in train mode, under autograd (train_aligner=True): (s2s_pred
+        [B, T_text + 1, n_token], s2s_attn [B, T_text, L] with the SOS step dropped, s2s_attn_mono); the search
+        itself stays under no_grad."""
+        from .align import mask_from_lens, maximum_path
+        if not self.text_aligner.training:
+            raise ValueError("TrainStep(train_aligner=True) needs the text aligner in train mode (.train())")
+        L = (mels.shape[-1] + 1) // 2
+        half = torch.as_tensor(mel_input_length).to(mels.device) // (2 ** self.text_aligner.n_down)
+        mask = torch.arange(L, device=mels.device)[None, :] + 1 > half[:, None]  # length_to_mask (:203)
+        _, s2s_pred, s2s_attn = self.text_aligner(mels, mask, texts, unk_mask=unk_mask)  # :206
+        s2s_attn = s2s_attn[:, 1:, :].contiguous()  # :207-209
+        with torch.no_grad():
+            mask_ST = mask_from_lens(s2s_attn, torch.as_tensor(input_lengths), half)
+            mono = maximum_path(s2s_attn.detach(), mask_ST)
+        return s2s_pred, s2s_attn, mono
+
     def _text_front(self, text):
         """train.py:217-251: the text encoder, asr, the predictor's forward and the crops."""
         from .prosody import matmul
@@ -217,7 +252,17 @@ class TrainStep:
         if self.text_encoder is None or self.predictor is None:
             raise ValueError("TrainStep(text=...) needs text_encoder= and predictor=")
         texts, lens = text["texts"], text["input_lengths"]
-        if "attn" in text or "attn_mono" in text:
+        self._aligner_out = None
+        if self.train_aligner:
+            if "attn" in text or "attn_mono" in text or "mel_input_length" not in text:
+                raise ValueError("TrainStep(train_aligner=True) computes the alignments itself: give "
+                                 "text['mel_input_length'] and neither attn nor attn_mono")
+            s2s_pred, attn, mono = self._align_train(text["mels"], text["mel_input_length"], texts, lens,
+                                                     text.get("unk_mask"))
+            self._aligner_out = (s2s_pred, attn, mono)
+            if text.get("mono", True):
+                attn = mono
+        elif "attn" in text or "attn_mono" in text:
             attn, mono = text["attn"], text["attn_mono"]
         else:  # train.py:203-214 from the aligner; `mono` stands in for the coin of :220
             if self.text_aligner is None or "mel_input_length" not in text:
@@ -240,10 +285,13 @@ class TrainStep:
         return en, p_en, gt, loss_dur, loss_ce
 
     def _step(self, en, F0, N, s, wav, noise, seed, p_en, gt, F0_real, N_real, text=None):
-        text_losses = None
+        text_losses, aligner_out = None, None
+        if self.train_aligner and text is None:
+            raise ValueError("TrainStep(train_aligner=True) needs the text= dict (the aligner runs on its mels)")
         if text is not None:
             en, p_en, gt, loss_dur, loss_ce = self._text_front(text)
             text_losses = (loss_dur, loss_ce)
+            aligner_out, self._aligner_out = self._aligner_out, None
         if self.style_encoder is not None and gt is not None:
             s = self.style_encoder(gt.unsqueeze(1))  # train.py:258
         if self.pitch_extractor is not None and gt is not None and F0_real is None and N_real is None:
@@ -281,6 +329,12 @@ class TrainStep:
             if text_losses is not None:  # train.py:300-307: lambda_ce loss_ce + lambda_dur loss_dur
                 extra["loss_dur"], extra["loss_ce"] = text_losses
                 g_loss = g_loss + self.lambda_ce * text_losses[1] + self.lambda_dur * text_losses[0]
+            if aligner_out is not None:  # train.py:301-306, 314-315
+                from .losses import mono_loss, s2s_loss
+                s2s_pred, s2s_attn, s2s_attn_mono = aligner_out
+                extra["loss_s2s"] = s2s_loss(s2s_pred, text["texts"], text["input_lengths"])
+                extra["loss_mono"] = mono_loss(s2s_attn, s2s_attn_mono)
+                g_loss = g_loss + self.lambda_mono * extra["loss_mono"] + self.lambda_s2s * extra["loss_s2s"]
             g_loss.backward()
         finally:
             for p in frozen:
@@ -289,11 +343,12 @@ class TrainStep:
             self.captured["dec"] = {k: p.grad.detach().clone() for k, p in self.decoder.named_parameters()
                                     if p.grad is not None}
             for tag, m in (("predictor", self.predictor), ("style_encoder", self.style_encoder),
-                           ("text_encoder", self.text_encoder)):
+                           ("text_encoder", self.text_encoder),
+                           ("text_aligner", self.text_aligner if self.train_aligner else None)):
                 if m is not None:
                     self.captured[tag] = {k: p.grad.detach().clone() for k, p in m.named_parameters()
                                           if p.grad is not None}
-        for key in ("predictor", "style_encoder", "decoder", "text_encoder"):  # train.py:323-327
+        for key in ("predictor", "style_encoder", "decoder", "text_encoder", "text_aligner"):  # train.py:323-328
             if key in self.opt:
                 self.opt[key].step()
         out = {"y_rec": y_rec.detach(), "d_loss": d_loss.detach(), "loss_mel": loss_mel.detach(),
